@@ -21,6 +21,12 @@ max-over-ranks); every rank decodes its own shard of the batch, no data-path
 collective: weak scaling. `--allgather` adds the benchmark_allgather.cpp
 exchange (compress shard -> all-gather compressed bytes -> decode remote shards).
 
+A plain run sets up, warms up, times `--steps` calls, checks their output (statuses, sizes, every byte) and prints
+the line: metric, value, ms_per_step (wall time of one timed step) and the workload. `--full` adds everything else:
+the roofline figures, the GPU compress leg, the other codecs' and batch sizes' lines (extras) and the CPU baselines. `--dump-outputs DIR` writes what the last timed step returned (a seeded sample of the decoded chunks, the
+actual sizes, the statuses) as .npy files: the inputs are the same from run to run, so two builds compare output for
+output.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -66,7 +72,16 @@ def parse_args():
     p.add_argument("--no-verify", action="store_true", help="(profiling of ablated kernels only) skip output checks")
     p.add_argument("--dry-run-emu", action="store_true",
                    help="CPU-only self-test of this script's plumbing against tests/emu (prints value=null)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline: roofline figures, the GPU compress leg, the other codecs' and "
+                        "batch sizes' lines and the CPU baselines (each still subject to the --no-* options above)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32 / float64): "
+                        "a seeded sample of the decoded chunks, the actual sizes and the statuses")
+    args = p.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the steps, check them, print the line
+        args.no_cpu_baseline = args.no_extras = args.no_riders = True
+    return args
 
 
 def cpu_compress(oracle, algo, chunks, producer, threads):
@@ -353,6 +368,15 @@ def run_case(args, ctx):
     elapsed = rt.max_over_ranks(time.perf_counter() - t0)
     kernel_ms = ev0.elapsed_time(ev1) / args.steps  # HIP events on the launch stream
 
+    if args.dump_outputs and rank == 0:
+        # chunk i of the batch is replica i // n_unique of unique chunk i % n_unique
+        pick = sample_indices(n, DUMP_CHUNKS)
+        offs = (pick // n_unique) * unique + raw_offs[pick % n_unique].astype(np.int64)
+        lens = raw_sizes[pick % n_unique].astype(np.int64)
+        dump_outputs(args.dump_outputs, out_slab, offs, lens, pick,
+                     dev.download(actual).view(np.uint64)[:n],
+                     None if statuses is None else dev.download(statuses).view(np.int32)[:n])
+
     # ---- verification (untimed): statuses, sizes, every output byte ----
     if args.no_verify:
         statuses, replicas_to_check = None, 0
@@ -414,7 +438,7 @@ def run_case(args, ctx):
             "sharding": "chunks partitioned across ranks, no collective" if world > 1 else "single GPU",
         },
     }
-    if rank == 0:
+    if rank == 0 and args.full:
         kernel = (f"{args.algo}_decompress_kernel" if own_format or args.algo == "deflate" else lz_decode_kernel(args.algo, n))
         result["roofline"] = roofline_block(kernel, algorithmic, kernel_ms, args.algo, "decompress", args.dataset, n, producer)
     if rank == 0 and world == 1 and not args.no_extras:
@@ -714,6 +738,43 @@ def library_source_digest(algo="lz4"):
     return h.hexdigest()[:16]
 
 
+DUMP_CHUNKS = 64  # decoded chunks --dump-outputs writes: 64 x 64 KiB as float32 = 16 MiB
+DUMP_PER_CHUNK = 1 << 20  # at most this many entries of the per-chunk arrays (index, size, status): 20 MiB
+
+
+def sample_indices(n, k, seed=0):
+    """All of range(n) when k >= n, else a fixed (seeded), sorted sample of k of them: the same for every build."""
+    if k >= n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirpath, out_buf, offs, lens, chunk_ids, actual, statuses):
+    """--dump-outputs: what the caller of the timed path holds after its last step, as DIR/<name>.npy. The decoded bytes
+    of the chunks `chunk_ids` (at `offs` / `lens` of `out_buf`) end to end, and the per-chunk actual sizes and statuses
+    (all of them, or a seeded sample of DUMP_PER_CHUNK where the batch is larger). Bytes, sizes up to 2^24 and statuses
+    are exact in float32; indices are float64."""
+    os.makedirs(dirpath, exist_ok=True)
+
+    def host(buf):  # a device tensor, a tensor over host memory (--dry-run-emu --allgather) or a numpy array
+        return buf.cpu().numpy() if hasattr(buf, "cpu") else np.asarray(buf)
+
+    parts = [host(out_buf[int(o): int(o) + int(s)]) for o, s in zip(offs, lens)]
+    decoded = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+    per_chunk = sample_indices(actual.size, DUMP_PER_CHUNK, seed=1)
+    arrays = {
+        "decompressed_sample": np.asarray(decoded, dtype=np.float32),
+        "decompressed_sample_chunks": np.asarray(chunk_ids, dtype=np.float64),
+        "decompressed_sample_sizes": np.asarray(lens, dtype=np.float64),
+        "actual_sizes_chunks": per_chunk.astype(np.float64),
+        "actual_sizes": np.asarray(actual, dtype=np.uint64)[per_chunk].astype(np.float64),
+    }
+    if statuses is not None:
+        arrays["statuses"] = np.asarray(statuses, dtype=np.int32)[per_chunk].astype(np.float32)
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirpath, f"{name}.npy"), arr)
+
+
 def finish(result, args, world, rt, data):
     if rt.dist is not None:
         digests = [None] * world
@@ -890,6 +951,11 @@ def run_allgather_case(args, ctx):
         step()
     rt.barrier_sync()
     elapsed = rt.max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        # rank 0's result: every shard (its own copied, the remote ones decoded), and the remote chunks' sizes / statuses
+        pick = sample_indices(world * n, DUMP_CHUNKS)
+        dump_outputs(args.dump_outputs, out, pick * CHUNK, np.full(pick.size, CHUNK, dtype=np.int64), pick,
+                     actual[:m].cpu().numpy().view(np.uint64), statuses[:m].cpu().numpy())
     if m:
         st = statuses[:m].cpu().numpy()
         assert (st == 0).all(), f"{int((st != 0).sum())} remote chunks failed"
@@ -946,7 +1012,7 @@ def rider(args, ctx, algo, **overrides):
 
     sargs = copy.copy(args)
     sargs.algo, sargs.no_extras, sargs.no_cpu_baseline, sargs.steps, sargs.warmup = algo, True, True, 5, 1
-    sargs.opts = ""
+    sargs.opts, sargs.dump_outputs = "", None
     compress_leg = overrides.pop("compress_leg", False)  # BASELINE.json configs[2] / [3] are round trips
     sargs.no_extras = not compress_leg
     for key, val in overrides.items():

@@ -10,7 +10,7 @@ for lib in nvcomp_amd/lib/alt/libnvcomp_*.so; do
   tag=$(basename $lib .so)
   for algo in ${ALGOS:-lz4}; do
     for mib in ${MIBS:-4096 1024}; do
-      NVCOMP_AMD_LIB=$PWD/$lib timeout 300 python bench.py --algo $algo --steps 5 --warmup 1 --no-cpu-baseline --no-extras --mib-per-gpu $mib --lz-index-min-batch 1000000000 > "$OUT/${tag}_${algo}_$mib.json" 2> "$OUT/${tag}_${algo}_$mib.err"
+      NVCOMP_AMD_LIB=$PWD/$lib timeout 300 python bench.py --full --algo $algo --steps 5 --warmup 1 --no-cpu-baseline --no-extras --mib-per-gpu $mib --lz-index-min-batch 1000000000 > "$OUT/${tag}_${algo}_$mib.json" 2> "$OUT/${tag}_${algo}_$mib.err"
       python - "$OUT/${tag}_${algo}_$mib.json" <<'PY'
 import json,sys
 f=sys.argv[1]

@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:-calib}
 mkdir -p "$OUT"
 pmc() { # name, env..., -- bench args
   local name=$1; shift
-  timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/$name" -o r -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-verify "$@" > "$OUT/$name.log" 2>&1
+  timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/$name" -o r -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-verify "$@" > "$OUT/$name.log" 2>&1
   python - "$OUT/$name/r_counter_collection.csv" "$name" <<'PY'
 import csv, sys, collections
 agg = collections.defaultdict(float); n = collections.defaultdict(set)

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 TAG=${1:-cascr}
 OUT=$PWD/gpurun_out/$TAG; mkdir -p "$OUT"
 timeout 200 python -m pytest tests/test_cascaded.py tests/test_cascaded_pins.py tests/test_golden_decode.py -m gpu -q -x 2>&1 | tail -2 | tee "$OUT/pytest.log"
-B="python bench.py --algo cascaded --dataset example_float_columns --mib-per-gpu 1024 --unique-mib 32 --no-cpu-baseline"
+B="python bench.py --full --algo cascaded --dataset example_float_columns --mib-per-gpu 1024 --unique-mib 32 --no-cpu-baseline"
 for rep in 1 2; do
   for lib in nvcomp_amd/lib/cab/libnvcomp_cascbase.so nvcomp_amd/lib/libnvcomp.so; do
     [ -f $lib ] || continue
@@ -19,8 +19,8 @@ import json,sys; r=json.loads(sys.stdin.read()); e=r.get('extras',{}); print(jso
 done
 ONLY="cascaded" bash scripts/gpu_traffic.sh "$TAG/traffic" > "$OUT/traffic.log" 2>&1; echo "traffic rc=$?" | tee -a "$OUT/rc.txt"
 [ -s "$OUT/traffic/pmc_traffic_r05.json" ] && cp "$OUT/traffic/pmc_traffic_r05.json" profiles/pmc_traffic_r05.json
-timeout 200 python bench.py --algo cascaded --no-riders > "$OUT/bench_cascaded.json" 2> "$OUT/bench_cascaded.err"; echo "bench cascaded rc=$?" | tee -a "$OUT/rc.txt"
-timeout 300 python bench.py > "$OUT/bench_lz4.json" 2> "$OUT/bench_lz4.err"; echo "bench lz4 rc=$?" | tee -a "$OUT/rc.txt"
+timeout 200 python bench.py --full --algo cascaded --no-riders > "$OUT/bench_cascaded.json" 2> "$OUT/bench_cascaded.err"; echo "bench cascaded rc=$?" | tee -a "$OUT/rc.txt"
+timeout 300 python bench.py --full > "$OUT/bench_lz4.json" 2> "$OUT/bench_lz4.err"; echo "bench lz4 rc=$?" | tee -a "$OUT/rc.txt"
 python - "$OUT" <<'PY'
 import json, sys, os
 o = sys.argv[1]

@@ -6,7 +6,7 @@ cd "$REPO"
 OUT=$REPO/gpurun_out/${1:-dpmc}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="python $REPO/bench.py --algo deflate --mib-per-gpu 1024 --unique-mib 32 --no-cpu-baseline --steps 2 --warmup 1"
+B="python $REPO/bench.py --full --algo deflate --mib-per-gpu 1024 --unique-mib 32 --no-cpu-baseline --steps 2 --warmup 1"
 cd /tmp
 pass() { local name=$1; shift
   timeout 200 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/pmc_$name" -o r -- $B > "$OUT/pmc_$name.log" 2>&1; echo "pmc $name rc=$?" >> "$OUT/rc.txt"; }

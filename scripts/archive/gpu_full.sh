@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; echo "smoke rc=$?" | tee "$OUT/rc.txt"
 timeout 1500 python -m pytest tests -m gpu -q --timeout 600 -x > "$OUT/pytest_gpu.log" 2>&1; echo "pytest rc=$?" | tee -a "$OUT/rc.txt"
 tail -5 "$OUT/pytest_gpu.log"
-timeout 600 python bench.py > "$OUT/bench_lz4.json" 2> "$OUT/bench_lz4.err"; echo "bench rc=$?" | tee -a "$OUT/rc.txt"
+timeout 600 python bench.py --full > "$OUT/bench_lz4.json" 2> "$OUT/bench_lz4.err"; echo "bench rc=$?" | tee -a "$OUT/rc.txt"
 python - "$OUT/bench_lz4.json" <<'PY'
 import json,sys
 r=json.load(open(sys.argv[1]))

@@ -9,7 +9,7 @@ IFS=';' read -ra SPECS <<< "${LINES}"
 i=0
 for spec in "${SPECS[@]}"; do
   i=$((i+1))
-  timeout 400 python bench.py --no-cpu-baseline $spec > "$OUT/line_$i.json" 2> "$OUT/line_$i.err"
+  timeout 400 python bench.py --full --no-cpu-baseline $spec > "$OUT/line_$i.json" 2> "$OUT/line_$i.err"
   python - "$OUT/line_$i.json" "$spec" <<'PY'
 import json,sys
 try:

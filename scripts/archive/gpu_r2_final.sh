@@ -10,11 +10,11 @@ OUT=$PWD/gpurun_out/${1:-r2final}
 mkdir -p "$OUT"; : > "$OUT/rc.txt"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; echo "smoke rc=$?" >> "$OUT/rc.txt"
 timeout 1500 python -m pytest tests -m gpu -q --timeout 900 > "$OUT/pytest_gpu.log" 2>&1; echo "pytest rc=$?" >> "$OUT/rc.txt"
-timeout 600 python bench.py > "$OUT/bench_lz4.json" 2> "$OUT/bench_lz4.err"; echo "bench lz4 rc=$?" >> "$OUT/rc.txt"
+timeout 600 python bench.py --full > "$OUT/bench_lz4.json" 2> "$OUT/bench_lz4.err"; echo "bench lz4 rc=$?" >> "$OUT/rc.txt"
 for a in snappy cascaded bitcomp ans deflate; do
-  timeout 400 python bench.py --algo $a > "$OUT/bench_$a.json" 2> "$OUT/bench_$a.err"; echo "bench $a rc=$?" >> "$OUT/rc.txt"
+  timeout 400 python bench.py --full --algo $a > "$OUT/bench_$a.json" 2> "$OUT/bench_$a.err"; echo "bench $a rc=$?" >> "$OUT/rc.txt"
 done
-B="python $REPO/bench.py --no-cpu-baseline --no-extras"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extras"
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o r -- $B --steps 5 --warmup 1 > "$OUT/trace.log" 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_snappy" -o r -- $B --algo snappy --steps 5 --warmup 1 > "$OUT/trace_snappy.log" 2>&1

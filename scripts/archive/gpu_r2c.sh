@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/${1:-r2c}
 mkdir -p "$OUT"
 timeout 1500 python -m pytest tests -m gpu -q --timeout 900 -x > "$OUT/pytest.log" 2>&1; echo "pytest rc=$?"; tail -4 "$OUT/pytest.log"
-timeout 600 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; echo "bench rc=$?"
+timeout 600 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; echo "bench rc=$?"
 python - "$OUT/bench_default.json" <<'PY'
 import json,sys
 r=json.load(open(sys.argv[1]))

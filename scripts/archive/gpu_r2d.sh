@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/${1:-r2d}
 mkdir -p "$OUT"
 timeout 600 python -m pytest tests/test_lz4_decode.py tests/test_snappy.py tests/test_fuzz_decode.py -m gpu -q -x > "$OUT/pytest.log" 2>&1; echo "pytest rc=$?"; tail -2 "$OUT/pytest.log"
-B="python bench.py --no-cpu-baseline --no-extras"
+B="python bench.py --full --no-cpu-baseline --no-extras"
 timeout 300 $B --dataset mortgage_col0_like --producer fast --unique-mib 314 --mib-per-gpu 314 --steps 20 --warmup 3 > "$OUT/mortgage_lz4_cpu.json" 2> "$OUT/mortgage_lz4_cpu.err"
 timeout 300 $B --algo snappy --dataset mortgage_col0_like --unique-mib 314 --mib-per-gpu 314 --steps 20 --warmup 3 > "$OUT/mortgage_snappy_cpu.json" 2>> "$OUT/mortgage_lz4_cpu.err"
 for algo in lz4 snappy; do

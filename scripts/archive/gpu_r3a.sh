@@ -18,5 +18,5 @@ for c, rs in rows.items():
 "
 tail -3 "$OUT/ab.err"
 if [ -f nvcomp_amd/lib/prof/libnvcomp_prof.so ]; then
-  NVCOMP_AMD_PROF=1 NVCOMP_AMD_LIB=$PWD/nvcomp_amd/lib/prof/libnvcomp_prof.so timeout 300 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --mib-per-gpu 1024 > "$OUT/prof_lz4.json" 2> "$OUT/prof_lz4.err"; tail -1 "$OUT/prof_lz4.err"
+  NVCOMP_AMD_PROF=1 NVCOMP_AMD_LIB=$PWD/nvcomp_amd/lib/prof/libnvcomp_prof.so timeout 300 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --mib-per-gpu 1024 > "$OUT/prof_lz4.json" 2> "$OUT/prof_lz4.err"; tail -1 "$OUT/prof_lz4.err"
 fi

@@ -25,7 +25,7 @@ for v in default wg4 wg2 wg1 ldsall; do
   for ctr in FETCH_SIZE WRITE_SIZE; do
     [ $ctr = WRITE_SIZE ] && [ $v != default ] && [ $v != ldsall ] && continue
     NVCOMP_AMD_LIB=$lib timeout 400 rocprofv3 --pmc $ctr --output-format csv -d "$OUT/pmc_${v}_$ctr" -o r -- \
-      python $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-riders > "$OUT/pmc_${v}_$ctr.log" 2>&1
+      python $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-riders > "$OUT/pmc_${v}_$ctr.log" 2>&1
     echo "pmc $v $ctr rc=$?" >> "$OUT/rc.txt"
   done
 done

@@ -16,16 +16,16 @@ if [ "${2:-}" != "notests" ]; then
 fi
 bash scripts/gpu_traffic.sh "$TAG/traffic" > "$OUT/traffic.log" 2>&1; echo "traffic rc=$?" >> "$OUT/rc.txt"
 [ -s "$OUT/traffic/pmc_traffic_r05.json" ] && cp "$OUT/traffic/pmc_traffic_r05.json" profiles/pmc_traffic_r05.json
-timeout 600 python bench.py > "$OUT/bench_lz4.json" 2> "$OUT/bench_lz4.err"; echo "bench lz4 rc=$?" >> "$OUT/rc.txt"
+timeout 600 python bench.py --full > "$OUT/bench_lz4.json" 2> "$OUT/bench_lz4.err"; echo "bench lz4 rc=$?" >> "$OUT/rc.txt"
 for a in snappy cascaded bitcomp ans deflate; do
-  timeout 400 python bench.py --algo $a --no-riders > "$OUT/bench_$a.json" 2> "$OUT/bench_$a.err"; echo "bench $a rc=$?" >> "$OUT/rc.txt"
+  timeout 400 python bench.py --full --algo $a --no-riders > "$OUT/bench_$a.json" 2> "$OUT/bench_$a.err"; echo "bench $a rc=$?" >> "$OUT/rc.txt"
 done
-B="python $REPO/bench.py --no-cpu-baseline --no-extras"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extras"
 cd /tmp
 for spec in "trace:" "trace_snappy:--algo snappy" "trace_deflate:--algo deflate" "trace_cascaded:--algo cascaded" "trace_bitcomp:--algo bitcomp" "trace_ans:--algo ans" "trace_compress:--extras-compress-only"; do
   name=${spec%%:*}; args=${spec#*:}
   if [ "$name" = trace_compress ]; then
-    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$name" -o r -- python $REPO/bench.py --no-cpu-baseline --no-riders --steps 3 --warmup 1 > "$OUT/$name.log" 2>&1
+    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$name" -o r -- python $REPO/bench.py --full --no-cpu-baseline --no-riders --steps 3 --warmup 1 > "$OUT/$name.log" 2>&1
   else
     timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$name" -o r -- $B $args --steps 5 --warmup 1 > "$OUT/$name.log" 2>&1
   fi
@@ -62,14 +62,14 @@ if ls nvcomp_amd/lib/cab/libnvcomp_cascprof.so > /dev/null 2>&1; then
 fi
 if ls nvcomp_amd/lib/cab/libnvcomp_lzwprof.so > /dev/null 2>&1; then
   for a in lz4 snappy; do
-    NVCOMP_AMD_PROF=1 NVCOMP_AMD_LIB=$PWD/nvcomp_amd/lib/cab/libnvcomp_lzwprof.so timeout 300 python bench.py --algo $a --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>&1 >/dev/null | grep phase_share | sed "s/^/{\"algo\": \"$a\", \"prof\": /; s/$/}/" >> "$OUT/decode_phases.jsonl"
+    NVCOMP_AMD_PROF=1 NVCOMP_AMD_LIB=$PWD/nvcomp_amd/lib/cab/libnvcomp_lzwprof.so timeout 300 python bench.py --full --algo $a --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>&1 >/dev/null | grep phase_share | sed "s/^/{\"algo\": \"$a\", \"prof\": /; s/$/}/" >> "$OUT/decode_phases.jsonl"
   done
 fi
 # Cascaded: one batch size per rocprofv3 summary, 1 GiB and 4 GiB of the reference's float columns
 cd /tmp
 for spec in "trace_cascaded_1g:--mib-per-gpu 1024 --unique-mib 32" "trace_cascaded_4g:"; do
   name=${spec%%:*}; args=${spec#*:}
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$name" -o r -- python $REPO/bench.py --algo cascaded --dataset example_float_columns --no-cpu-baseline --no-extras $args --steps 5 --warmup 1 > "$OUT/$name.log" 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$name" -o r -- python $REPO/bench.py --full --algo cascaded --dataset example_float_columns --no-cpu-baseline --no-extras $args --steps 5 --warmup 1 > "$OUT/$name.log" 2>&1
 done
 cd "$REPO"
 [ "${HARNESS:-1}" = 1 ] && bash scripts/gpu_r4_harness.sh "$TAG/harness" > "$OUT/harness_run.log" 2>&1

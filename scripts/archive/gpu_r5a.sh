@@ -20,7 +20,7 @@ for l in open(os.path.join(sys.argv[1], "ab_comp.jsonl")):
 PY
 tail -5 "$OUT/ab_comp.err"
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?" >> "$OUT/rc.txt"
+  timeout 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?" >> "$OUT/rc.txt"
   python -c "
 import json,sys
 r=json.load(open('$OUT/bench.json')); e=r['extras']

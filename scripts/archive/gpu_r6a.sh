@@ -32,7 +32,7 @@ PY
   tail -3 "$OUT/ab_dec.err"
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?" >> "$OUT/rc.txt"
+  timeout 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?" >> "$OUT/rc.txt"
   python - "$OUT" <<'PY'
 import json, sys, os
 x = json.loads(open(os.path.join(sys.argv[1], "bench.json")).read().strip().splitlines()[-1])

@@ -25,7 +25,7 @@ PY
   tail -3 "$OUT/ab_dec.err"
 fi
 if [ "${5:-0}" = 1 ]; then
-  timeout 900 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?" >> "$OUT/rc.txt"
+  timeout 900 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?" >> "$OUT/rc.txt"
   tail -c 2500 "$OUT/bench.json"
 fi
 cat "$OUT/rc.txt"

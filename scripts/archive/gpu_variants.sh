@@ -7,8 +7,8 @@ OUT=gpurun_out/${1:-var}
 mkdir -p "$OUT"
 for lib in nvcomp_amd/lib/libnvcomp.so nvcomp_amd/lib/alt/libnvcomp_*.so; do
   tag=$(basename $lib .so)
-  NVCOMP_AMD_LIB=$PWD/$lib timeout 300 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extras --no-verify > "$OUT/$tag.json" 2> "$OUT/$tag.err"
-  NVCOMP_AMD_LIB=$PWD/$lib timeout 300 python bench.py --algo snappy --steps 5 --warmup 1 --no-cpu-baseline --no-extras --no-verify > "$OUT/${tag}_snappy.json" 2>> "$OUT/$tag.err"
+  NVCOMP_AMD_LIB=$PWD/$lib timeout 300 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-extras --no-verify > "$OUT/$tag.json" 2> "$OUT/$tag.err"
+  NVCOMP_AMD_LIB=$PWD/$lib timeout 300 python bench.py --full --algo snappy --steps 5 --warmup 1 --no-cpu-baseline --no-extras --no-verify > "$OUT/${tag}_snappy.json" 2>> "$OUT/$tag.err"
   python - "$OUT/$tag.json" "$OUT/${tag}_snappy.json" <<'PY'
 import json,sys
 for f in sys.argv[1:]:

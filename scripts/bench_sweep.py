@@ -24,7 +24,7 @@ def main():
     ap.add_argument("--unchecked-too", action="store_true")
     ap.add_argument("--dry-run-emu", action="store_true")
     a = ap.parse_args()
-    sys.argv = [sys.argv[0]]
+    sys.argv = [sys.argv[0], "--full"]  # every case reads the roofline figures and the compress leg
     base = bench.parse_args()
     base.dry_run_emu = a.dry_run_emu
     ctx = bench.setup_runtime(base)

@@ -19,7 +19,7 @@ lib = nvcomp_amd.load_library()
 import bench  # noqa: E402
 
 sys.argv = ["bench.py", "--algo", "cascaded", "--dataset", ds, "--mib-per-gpu", mib, "--unique-mib", "32", "--steps", "3", "--warmup", "1",
-            "--no-cpu-baseline"] + ([] if compress else ["--no-extras"])
+            "--full", "--no-cpu-baseline"] + ([] if compress else ["--no-extras"])
 slots = (C.c_ulonglong * 12)()
 lib.nvcompAmdCascProfRead(slots, 12)  # clear
 try:

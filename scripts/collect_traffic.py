@@ -28,7 +28,7 @@ KERNELS = {
     "lz4_16384": [("lz4_decompress_window_kernel", "lz4", "decompress")],
     "lz4_4096": [("lz4_decompress_pair_kernel", "lz4", "decompress")],
     "lz4_256": [("lz4_decompress_team_kernel", "lz4", "decompress")],
-    # the other codecs' own bench lines (python bench.py --algo X at its default size)
+    # the other codecs' own bench lines (python bench.py --full --algo X at its default size)
     "cascaded_line": [("cascaded_decompress_kernel", "cascaded", "decompress")],
     "bitcomp_line": [("bitcomp_decompress_kernel", "bitcomp", "decompress")],
     "ans_line": [("ans_decompress_kernel", "ans", "decompress")],

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 TAG=$1; KERN=$2; shift 2
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p "$OUT"
-B="python $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras $*"
+B="python $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras $*"
 cd /tmp
 pass() { local name=$1; shift
   timeout 300 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/pmc_$name" -o r -- $B > "$OUT/pmc_$name.log" 2>&1; echo "pmc $name rc=$?" >> "$OUT/rc.txt"; }

@@ -13,15 +13,15 @@ import json,sys; r=json.loads(sys.stdin.read()); e=r.get('extras',{}); print('$1
 for rep in 1 2 3; do
   for which in new ${VARIANTS:-cascold}; do
     if [ $which != new ]; then export NVCOMP_AMD_LIB=$PWD/nvcomp_amd/lib/cab/libnvcomp_$which.so; else unset NVCOMP_AMD_LIB; fi
-    python bench.py --algo cascaded --mib-per-gpu 1024 --unique-mib 32 --no-cpu-baseline 2>/dev/null | tee -a "$OUT/lines_${which}.jsonl" | line "$which 1GiB"
-    python bench.py --algo cascaded --no-cpu-baseline 2>/dev/null | tee -a "$OUT/lines_${which}.jsonl" | line "$which 4GiB"
+    python bench.py --full --algo cascaded --mib-per-gpu 1024 --unique-mib 32 --no-cpu-baseline 2>/dev/null | tee -a "$OUT/lines_${which}.jsonl" | line "$which 1GiB"
+    python bench.py --full --algo cascaded --no-cpu-baseline 2>/dev/null | tee -a "$OUT/lines_${which}.jsonl" | line "$which 4GiB"
     for mib in ${SMALL:-16 64 256}; do
-      python bench.py --algo cascaded --mib-per-gpu $mib --unique-mib 16 --no-cpu-baseline 2>/dev/null | tee -a "$OUT/lines_${which}.jsonl" | line "$which ${mib}MiB"
+      python bench.py --full --algo cascaded --mib-per-gpu $mib --unique-mib 16 --no-cpu-baseline 2>/dev/null | tee -a "$OUT/lines_${which}.jsonl" | line "$which ${mib}MiB"
     done
   done
 done
 unset NVCOMP_AMD_LIB
-rocprofv3 --kernel-trace --stats -d "$OUT/trace_1g" -o r -- python bench.py --algo cascaded --mib-per-gpu 1024 --unique-mib 32 --no-cpu-baseline --steps 5 --warmup 1 > "$OUT/trace_1g.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$OUT/trace_1g" -o r -- python bench.py --full --algo cascaded --mib-per-gpu 1024 --unique-mib 32 --no-cpu-baseline --steps 5 --warmup 1 > "$OUT/trace_1g.log" 2>&1
 python - "$OUT" <<'PY'
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + "/trace_1g/**/r_kernel_trace.csv", recursive=True):

@@ -14,8 +14,8 @@ for rep in 1 2 3; do
     if [ $which != new ]; then export NVCOMP_AMD_LIB=$PWD/nvcomp_amd/lib/alt/libnvcomp_$which.so; else unset NVCOMP_AMD_LIB; fi
     for ds in ${DATASETS:-default}; do
       dsarg=""; [ $ds != default ] && dsarg="--dataset $ds"
-      python bench.py --algo $ALGO $dsarg --mib-per-gpu 1024 --unique-mib 32 --no-cpu-baseline 2>/dev/null | tee -a "$OUT/lines_${which}.jsonl" | line "$which $ds 1GiB"
-      python bench.py --algo $ALGO $dsarg --no-cpu-baseline 2>/dev/null | tee -a "$OUT/lines_${which}.jsonl" | line "$which $ds default"
+      python bench.py --full --algo $ALGO $dsarg --mib-per-gpu 1024 --unique-mib 32 --no-cpu-baseline 2>/dev/null | tee -a "$OUT/lines_${which}.jsonl" | line "$which $ds 1GiB"
+      python bench.py --full --algo $ALGO $dsarg --no-cpu-baseline 2>/dev/null | tee -a "$OUT/lines_${which}.jsonl" | line "$which $ds default"
     done
   done
 done

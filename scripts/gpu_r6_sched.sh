@@ -10,7 +10,7 @@ for a in cascaded ans bitcomp deflate; do
   ds=""; [ $a = cascaded ] && ds="--dataset example_float_columns"
   for lib in default ilpall; do
     if [ $lib = default ]; then unset NVCOMP_AMD_LIB; else export NVCOMP_AMD_LIB=$PWD/nvcomp_amd/lib/ilpall/libnvcomp.so; fi
-    timeout 300 python bench.py --algo $a $ds --mib-per-gpu 1024 --unique-mib 32 --no-cpu-baseline --no-riders --steps 10 --warmup 2 2>/dev/null | python -c "
+    timeout 300 python bench.py --full --algo $a $ds --mib-per-gpu 1024 --unique-mib 32 --no-cpu-baseline --no-riders --steps 10 --warmup 2 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

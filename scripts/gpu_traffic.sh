@@ -9,7 +9,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 OUT=gpurun_out/${1:-traffic}
 mkdir -p "$OUT"
-B="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-riders"
+B="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-riders"
 run() { # name, bench args...   (ONLY="name name": just these, and the result is merged into the committed record)
   local name=$1; shift
   if [ -n "${ONLY:-}" ] && ! echo " $ONLY " | grep -q " $name "; then return; fi

@@ -131,13 +131,13 @@ def test_allgather_program_oversubscribed(built_programs, sample_files):
 @pytest.mark.gpu
 @pytest.mark.parametrize("algo", ["lz4", "snappy", "cascaded", "bitcomp", "ans", "deflate"])
 def test_bench_contract_on_gpu(algo):
-    """bench.py prints exactly one JSON line with the driver's fields plus `roofline` and `cpu_baseline`, measures
+    """bench.py --full prints exactly one JSON line with the driver's fields plus `roofline` and `cpu_baseline`, measures
     through HIP events on its stream and verifies every decoded byte (small workload: 64 MiB per step)."""
     import json
     import sys
 
-    r = subprocess.run([sys.executable, "bench.py", "--algo", algo, "--steps", "3", "--warmup", "1", "--mib-per-gpu", "64",
-                        "--unique-mib", "8"], cwd=REPO, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--algo", algo, "--steps", "3", "--warmup", "1", "--mib-per-gpu",
+                        "64", "--unique-mib", "8"], cwd=REPO, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -152,6 +152,31 @@ def test_bench_contract_on_gpu(algo):
     assert abs(roof["frac"] - roof["achieved"] / roof["peak"]) < 1e-3
     base = res["cpu_baseline"]
     assert base["value"] > 0 and base["cores"] >= 1 and base["kind"] in ("reference", "port") and base["sample"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_outputs_on_gpu(tmp_path):
+    """A plain bench.py run: the headline line without the --full parts, and --dump-outputs writes the decoded bytes of
+    the last timed step (a seeded sample of the chunks: every replica holds the generator's bytes), sizes and statuses."""
+    import json
+    import sys
+
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--mib-per-gpu", "64", "--unique-mib",
+                        "8", "--dump-outputs", str(tmp_path)], cwd=REPO, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["value"] > 1.0 and res["ms_per_step"] > 0 and res["config"]["verified"] is True
+    assert "roofline" not in res and "extras" not in res and "cpu_baseline" not in res
+    data = datasets.silesia_style(8 << 20, 0)
+    chunks = np.load(tmp_path / "decompressed_sample_chunks.npy").astype(np.int64)
+    sample = np.load(tmp_path / "decompressed_sample.npy")
+    assert chunks.size == 64 and sample.dtype == np.float32 and sample.size == 64 * 65536
+    want = np.concatenate([data[(c % 128) * 65536: (c % 128 + 1) * 65536] for c in chunks])
+    assert np.array_equal(sample, want.astype(np.float32))
+    assert (np.load(tmp_path / "actual_sizes.npy") == 65536).all() and (np.load(tmp_path / "statuses.npy") == 0).all()
+    assert np.load(tmp_path / "actual_sizes.npy").size == 1024
 
 
 @pytest.mark.gpu

@@ -1,6 +1,6 @@
 """benchmarks/text_to_binary.py (ours) against the output of the reference's own script on the reference's own fixture
-(tests/golden/ExampleFloatData_col*_float.bin, scripts/make_golden_columns.py), and -- when the reference tree is
-present, i.e. in the build container -- against the source CSV directly."""
+(tests/golden/ExampleFloatData_col*_float.bin, scripts/make_golden_columns.py), and against that fixture's source CSV
+(tests/golden/ExampleFloatData.csv.gz) directly."""
 import hashlib
 import json
 import os
@@ -8,11 +8,10 @@ import subprocess
 import sys
 
 import numpy as np
-import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(REPO, "tests", "golden")
-REF_CSV = "/root/reference/benchmarks/ExampleFloatData.csv"
+REF_CSV_GZ = os.path.join(GOLD, "ExampleFloatData.csv.gz")
 
 
 def test_fixtures_are_what_the_manifest_says():
@@ -52,10 +51,14 @@ def test_round_trip_through_our_tool(tmp_path):
     assert np.fromfile(tmp_path / "d.bin", dtype=np.float64).tolist() == [2.5, 1e-3]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CSV), reason="the reference tree is only in the build container")
 def test_same_bytes_as_the_reference_script(tmp_path):
+    import gzip
+
+    ref_csv = tmp_path / "ExampleFloatData.csv"
+    with gzip.open(REF_CSV_GZ, "rb") as f:
+        ref_csv.write_bytes(f.read())
     for c in range(3):
         out = tmp_path / f"c{c}.bin"
-        subprocess.run([sys.executable, os.path.join(REPO, "benchmarks", "text_to_binary.py"), REF_CSV, str(c), "float", str(out)],
+        subprocess.run([sys.executable, os.path.join(REPO, "benchmarks", "text_to_binary.py"), str(ref_csv), str(c), "float", str(out)],
                        check=True, capture_output=True)
         assert open(out, "rb").read() == open(os.path.join(GOLD, f"ExampleFloatData_col{c}_float.bin"), "rb").read()

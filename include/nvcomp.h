@@ -18,5 +18,6 @@
 #include "nvcomp/ans.h"
 #include "nvcomp/deflate.h"
 #include "nvcomp/gzip.h"
+#include "nvcomp/zstd.h"
 
 #endif /* NVCOMP_H */

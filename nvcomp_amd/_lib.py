@@ -86,6 +86,8 @@ EXTRA_ENTRY_POINTS = {
 }
 # include/nvcomp/gzip.h: decompression only
 GZIP_ENTRY_POINTS = ("DecompressGetTempSize", "DecompressGetTempSizeEx", "DecompressAsync", "GetDecompressSizeAsync")
+# include/nvcomp/zstd.h: decompression only (not in FORMATS, which export a compressor)
+ZSTD_ENTRY_POINTS = ("DecompressGetTempSize", "DecompressGetTempSizeEx", "DecompressAsync", "GetDecompressSizeAsync")
 
 
 def build_library(verbose: bool = False) -> str:
@@ -121,6 +123,13 @@ def declare(lib: C.CDLL, formats=FORMATS) -> C.CDLL:
         lib.nvcompBatchedGzipGetDecompressSizeAsync.argtypes = [vp, vp, vp, sz, vp]
         for name in GZIP_ENTRY_POINTS:
             getattr(lib, "nvcompBatchedGzip" + name).restype = C.c_int
+    if hasattr(lib, "nvcompBatchedZstdDecompressAsync"):  # include/nvcomp/zstd.h
+        lib.nvcompBatchedZstdDecompressGetTempSize.argtypes = [sz, sz, szp]
+        lib.nvcompBatchedZstdDecompressGetTempSizeEx.argtypes = [sz, sz, szp, sz]
+        lib.nvcompBatchedZstdDecompressAsync.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, vp, vp]
+        lib.nvcompBatchedZstdGetDecompressSizeAsync.argtypes = [vp, vp, vp, sz, vp]
+        for name in ZSTD_ENTRY_POINTS:
+            getattr(lib, "nvcompBatchedZstd" + name).restype = C.c_int
     if hasattr(lib, "nvcompAmdBatchedPackAsync"):  # include/nvcomp/amd_ext.h
         lib.nvcompAmdBatchedPackAsync.argtypes = [vp, vp, sz, vp, sz, vp, vp]
     for fmt in ("LZ4", "Snappy"):

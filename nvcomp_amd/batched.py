@@ -131,6 +131,9 @@ class BatchedCodec:
         if fmt == "Gzip":  # include/nvcomp/gzip.h: decompression only, no options
             self.opts_t = self.opts = None
             return
+        if fmt == "Zstd":  # include/nvcomp/zstd.h: decompression only, no options
+            self.opts_t = self.opts = None
+            return
         self.opts_t = OPTS[fmt]
         if opts is None:
             opts = {"LZ4": (0,), "Snappy": (0,), "Cascaded": (4096, 4, 2, 1, 1), "Bitcomp": (0, 1), "ANS": (0,),

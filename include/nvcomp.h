@@ -19,5 +19,6 @@
 #include "nvcomp/deflate.h"
 #include "nvcomp/gzip.h"
 #include "nvcomp/zstd.h"
+#include "nvcomp/crc32.h"
 
 #endif /* NVCOMP_H */

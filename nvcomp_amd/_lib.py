@@ -130,6 +130,9 @@ def declare(lib: C.CDLL, formats=FORMATS) -> C.CDLL:
         lib.nvcompBatchedZstdGetDecompressSizeAsync.argtypes = [vp, vp, vp, sz, vp]
         for name in ZSTD_ENTRY_POINTS:
             getattr(lib, "nvcompBatchedZstd" + name).restype = C.c_int
+    if hasattr(lib, "nvcompBatchedCRC32Async"):  # include/nvcomp/crc32.h
+        lib.nvcompBatchedCRC32Async.argtypes = [vp, vp, sz, vp, vp]
+        lib.nvcompBatchedCRC32Async.restype = C.c_int
     if hasattr(lib, "nvcompAmdBatchedPackAsync"):  # include/nvcomp/amd_ext.h
         lib.nvcompAmdBatchedPackAsync.argtypes = [vp, vp, sz, vp, sz, vp, vp]
     for fmt in ("LZ4", "Snappy"):

@@ -243,3 +243,21 @@ class BatchedCodec:
         self._check(self.get_decompress_size_async(comp, sizes), self._p + "GetDecompressSizeAsync")
         d.synchronize()
         return d.download(sizes).view(np.uint64)[:n].copy()
+
+
+def crc32_async(lib: C.CDLL, dev, batch: DeviceBatch, out) -> int:
+    """``nvcompBatchedCRC32Async`` over a resident batch into the device buffer ``out`` (``batch.count`` uint32)."""
+    return lib.nvcompBatchedCRC32Async(dev.ptr(batch.ptrs), dev.ptr(batch.sizes), batch.count, dev.ptr(out),
+                                       dev.stream())
+
+
+def crc32(lib: C.CDLL, dev, chunks: Sequence[np.ndarray], align: int = 1) -> np.ndarray:
+    """Standard CRC-32 of every chunk (include/nvcomp/crc32.h): what zlib.crc32 gives, as uint32."""
+    n = len(chunks)
+    batch = make_batch(dev, chunks, align=align)
+    out = dev.empty(4 * n)
+    rc = crc32_async(lib, dev, batch, out)
+    if rc != NvcompStatus.Success:
+        raise RuntimeError(f"nvcompBatchedCRC32Async returned {rc}")
+    dev.synchronize()
+    return dev.download(out, 4 * n).view(np.uint32).copy()

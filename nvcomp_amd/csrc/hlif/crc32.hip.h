@@ -19,6 +19,10 @@
  *
  * The tables (8 KiB: slicing and skipping) and the six constants are computed at COMPILE time (constexpr) and copied to
  * LDS once per workgroup. Rounds 1-2 walked a chunk with ONE THREAD, a dependent table lookup per byte.
+ *
+ * The core (wave_crc32_raw) returns the raw remainder from a given initial state, without the final complement, so a
+ * chunk can also be cut into segments for several waves and put back together: api/crc32_api.hip multiplies each
+ * segment's remainder by x^(8 * bytes after it) (append_zeros) and XORs the parts.
  */
 #pragma once
 
@@ -156,16 +160,18 @@ struct Piece
   }
 };
 
-/* CRC-32 of p[0, n) with the calling wave (n < 2^31); `lds` = the tables (load_tables). The result is wave-uniform.
- * (Issuing the loads of tile t + 1 before the lookups of tile t was measured and changes nothing: the other waves of the
- * CU fill the gaps. scripts/probes/crc_bench.hip: loads alone 6.0 TB/s, lookups alone 9.2, the kernel 4.9.) */
+/* The RAW remainder of p[0, n) with the calling wave (n < 2^31), from the state `init` the chain had in front of p[0]
+ * (0xffffffff at the start of a message, 0 in front of a segment that is combined later); no final complement. `lds` =
+ * the tables (load_tables). The result is wave-uniform. (Issuing the loads of tile t + 1 before the lookups of tile t
+ * was measured and changes nothing: the other waves of the CU fill the gaps. scripts/probes/crc_bench.hip: loads alone
+ * 6.0 TB/s, lookups alone 9.2, the kernel 4.9.) */
 template <uint32_t kSeg = kSegDefault>
-__device__ __forceinline__ uint32_t wave_crc32(const uint8_t* p, uint32_t n, const uint32_t* lds)
+__device__ __forceinline__ uint32_t wave_crc32_raw(const uint8_t* p, uint32_t n, uint32_t init, const uint32_t* lds)
 {
   static_assert(kSeg == 16 || kSeg == 32 || kSeg == 64, "one, two or four 16-byte loads per lane and tile");
   constexpr uint32_t kTile = 64 * kSeg;
   if (n == 0) {
-    return 0;
+    return init;
   }
   const uint32_t lane = (uint32_t)wave::lane_id();
   const uint32_t* slice = lds;
@@ -179,10 +185,10 @@ __device__ __forceinline__ uint32_t wave_crc32(const uint8_t* p, uint32_t n, con
   /* the first tile: the message starts somewhere inside it */
   if (v0 >= pad) {
     cur.load(q);
-    s = cur.into(slice, v0 == pad ? 0xffffffffu : 0u); /* the message starts here: every CRC-32 starts from all ones */
+    s = cur.into(slice, v0 == pad ? init : 0u); /* the message starts here: the chain's state enters with its first byte */
   } else if (v0 + kSeg > pad) {
     /* the message starts inside my bytes: byte by byte from its first byte on */
-    s = 0xffffffffu;
+    s = init;
     for (uint32_t i = pad - v0; i < kSeg; ++i) {
       s = slice[(s ^ wave::gload_u8(q + i)) & 0xffu] ^ (s >> 8);
     }
@@ -207,7 +213,53 @@ __device__ __forceinline__ uint32_t wave_crc32(const uint8_t* p, uint32_t n, con
   x ^= wave::shuffle(x, lane ^ 4u);
   x ^= wave::shuffle(x, lane ^ 2u);
   x ^= wave::shuffle(x, lane ^ 1u);
-  return wave::uniform(x) ^ 0xffffffffu;
+  return wave::uniform(x);
+}
+
+/* The same for any length: pieces of kLongPiece bytes (a whole number of tiles), each entering with the state the
+ * previous one left. */
+constexpr uint32_t kLongPiece = 1u << 30;
+template <uint32_t kSeg = kSegDefault>
+__device__ __forceinline__ uint32_t wave_crc32_raw_long(const uint8_t* p, uint64_t n, uint32_t init, const uint32_t* lds)
+{
+  uint32_t s = init;
+  for (; n > kLongPiece; p += kLongPiece, n -= kLongPiece) {
+    s = wave_crc32_raw<kSeg>(p, kLongPiece, s, lds);
+  }
+  return wave_crc32_raw<kSeg>(p, (uint32_t)n, s, lds);
+}
+
+/* CRC-32 of p[0, n) with the calling wave (n < 2^31): the raw remainder from all ones, complemented. */
+template <uint32_t kSeg = kSegDefault>
+__device__ __forceinline__ uint32_t wave_crc32(const uint8_t* p, uint32_t n, const uint32_t* lds)
+{
+  return wave_crc32_raw<kSeg>(p, n, 0xffffffffu, lds) ^ 0xffffffffu;
+}
+
+/* x^(8 * 2^k) mod P for k < 64: appending 2^k zero bytes (the combine of segments: s * x^(8 E) by square-and-multiply
+ * over the bits of E) */
+struct BytePowers
+{
+  uint32_t v[64];
+  constexpr BytePowers() : v()
+  {
+    v[0] = xpow_bytes(1);
+    for (uint32_t k = 1; k < 64; ++k) {
+      v[k] = mulmod(v[k - 1], v[k - 1]);
+    }
+  }
+};
+__constant__ static const BytePowers kBytePowers = BytePowers();
+
+/* s * x^(8 e) mod P: the raw remainder s followed by e zero bytes (s and e wave-uniform) */
+__device__ __forceinline__ uint32_t append_zeros(uint32_t s, uint64_t e)
+{
+  for (uint32_t k = 0; e != 0; ++k, e >>= 1) {
+    if (e & 1u) {
+      s = mul_const(s, kBytePowers.v[k]);
+    }
+  }
+  return s;
 }
 
 } // namespace crc32w

@@ -14,7 +14,6 @@
 namespace {
 
 constexpr unsigned kWavesPerBlock = 4;
-constexpr uint32_t kMaxOutCap = 1u << 26;
 
 __global__ void __launch_bounds__(64 * kWavesPerBlock) ans_compress_kernel(
     const void* const* __restrict__ in_ptrs,
@@ -59,15 +58,16 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) ans_decompress_kernel(
   uint8_t* out = wave::uniform_ptr((uint8_t*)out_ptrs[chunk]);
   const size_t in_len64 = wave::uniform64(comp_bytes[chunk]);
   size_t cap64 = wave::uniform64(out_caps[chunk]);
-  if (cap64 > kMaxOutCap) {
-    cap64 = kMaxOutCap;
+  if (cap64 > ans::kMaxOutCap) {
+    cap64 = ans::kMaxOutCap;
   }
   uint32_t err = ans::kErrNone;
   uint32_t produced = 0;
   if (in_len64 > 0xffffffffull - 64) {
     err = ans::kErrInput;
   } else {
-    produced = ans::decode_chunk(in, (uint32_t)in_len64, out, (uint32_t)cap64, lds[w], err);
+    ans::MemoryOut o{out};
+    produced = ans::decode_chunk(in, (uint32_t)in_len64, o, (uint32_t)cap64, lds[w], err);
   }
   if (wave::lane_id() == 0) {
     if (actual_bytes != nullptr) {
@@ -88,7 +88,7 @@ __global__ void __launch_bounds__(256) ans_decompress_size_kernel(
   }
   const uint8_t* in = (const uint8_t*)comp_ptrs[chunk];
   size_t n = 0;
-  if (comp_bytes[chunk] >= ans::kHeaderBytes && ans::load_as<uint32_t>(in) == 0x01534e41u) {
+  if (comp_bytes[chunk] >= ans::kHeaderBytes && ans::load_as<uint32_t>(in) == ans::kMagic) {
     n = ans::load_as<uint32_t>(in + 4);
   }
   out_bytes[chunk] = n;

@@ -133,6 +133,27 @@ def declare(lib: C.CDLL, formats=FORMATS) -> C.CDLL:
     if hasattr(lib, "nvcompBatchedCRC32Async"):  # include/nvcomp/crc32.h
         lib.nvcompBatchedCRC32Async.argtypes = [vp, vp, sz, vp, vp]
         lib.nvcompBatchedCRC32Async.restype = C.c_int
+    if hasattr(lib, "bitcompCreatePlan"):  # include/nvcomp/native/bitcomp.h
+        h = vp  # bitcompHandle_t
+        for name, args in (
+                ("bitcompCreatePlan", [C.POINTER(vp), sz, C.c_int, C.c_int, C.c_int]),
+                ("bitcompCreatePlanFromCompressedData", [C.POINTER(vp), vp]),
+                ("bitcompDestroyPlan", [h]),
+                ("bitcompSetStream", [h, vp]),
+                ("bitcompCompressLossless", [h, vp, vp]),
+                ("bitcompCompressLossy_fp16", [h, vp, vp, C.c_float]),
+                ("bitcompCompressLossy_fp32", [h, vp, vp, C.c_float]),
+                ("bitcompCompressLossy_fp64", [h, vp, vp, C.c_double]),
+                ("bitcompUncompress", [h, vp, vp]),
+                ("bitcompPartialUncompress", [h, vp, vp, sz, sz]),
+                ("bitcompGetCompressedSize", [vp, szp]),
+                ("bitcompGetCompressedSizeAsync", [vp, vp, vp]),
+                ("bitcompGetUncompressedSize", [vp, szp]),
+                ("bitcompGetUncompressedSizeFromHandle", [h, szp]),
+                ("bitcompGetCompressedInfo", [vp, sz, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)])):
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = args, C.c_int
+        lib.bitcompMaxBuflen.argtypes, lib.bitcompMaxBuflen.restype = [sz], sz
     if hasattr(lib, "nvcompAmdBatchedPackAsync"):  # include/nvcomp/amd_ext.h
         lib.nvcompAmdBatchedPackAsync.argtypes = [vp, vp, sz, vp, sz, vp, vp]
     for fmt in ("LZ4", "Snappy"):

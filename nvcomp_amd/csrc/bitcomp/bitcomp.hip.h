@@ -198,8 +198,70 @@ struct PackedRow<uint16_t>
   using type = uint32_t;
 };
 
-template <class T, bool DELTA>
-__device__ __forceinline__ uint32_t encode_chunk(const uint8_t* __restrict__ src, uint32_t n, uint8_t* __restrict__ dst)
+/* What the block loader does to an element on its way in (compress) and the block storer on its way out (decompress).
+ * The batched codec moves the elements as they are; the native API (api/bitcomp_native_api.hip, bitcomp/quantize.hip.h)
+ * quantises floating-point elements to integers here and restores them there, and stores only a range of a segment for
+ * partial decompression -- in the same loads and stores, so the lossy path moves the bytes the lossless one moves. `in`
+ * and `out` see an element as the unsigned integer of its width; `keep(i)` says whether element i of the chunk is stored. */
+struct AsIs
+{
+  static constexpr bool kIdentity = true;
+  template <class T>
+  __device__ __forceinline__ T in(T v) const
+  {
+    return v;
+  }
+  template <class T>
+  __device__ __forceinline__ T out(T v) const
+  {
+    return v;
+  }
+  __device__ __forceinline__ bool keep(uint32_t) const
+  {
+    return true;
+  }
+};
+
+/* `in` / `out` over a lane's values of one row: the element itself, or the E small ones of a dword */
+template <class T, class X>
+__device__ __forceinline__ typename PackedRow<T>::type row_in(const X& x, typename PackedRow<T>::type raw)
+{
+  using Z = typename PackedRow<T>::type;
+  if (X::kIdentity) {
+    return raw;
+  }
+  if (sizeof(T) >= 4) {
+    return (Z)x.template in<T>((T)raw);
+  }
+  uint32_t r = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 4 / sizeof(T); ++k) {
+    r |= (uint32_t)x.template in<T>((T)((uint32_t)raw >> (8 * sizeof(T) * k))) << (8 * sizeof(T) * k);
+  }
+  return (Z)r;
+}
+
+template <class T, class X>
+__device__ __forceinline__ typename PackedRow<T>::type row_out(const X& x, typename PackedRow<T>::type v)
+{
+  using Z = typename PackedRow<T>::type;
+  if (X::kIdentity) {
+    return v;
+  }
+  if (sizeof(T) >= 4) {
+    return (Z)x.template out<T>((T)v);
+  }
+  uint32_t r = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 4 / sizeof(T); ++k) {
+    r |= (uint32_t)x.template out<T>((T)((uint32_t)v >> (8 * sizeof(T) * k))) << (8 * sizeof(T) * k);
+  }
+  return (Z)r;
+}
+
+template <class T, bool DELTA, class X = AsIs>
+__device__ __forceinline__ uint32_t encode_chunk(
+    const uint8_t* __restrict__ src, uint32_t n, uint8_t* __restrict__ dst, const X x = X())
 {
   constexpr uint32_t S = sizeof(T);
   const uint32_t lane = (uint32_t)wave::lane_id();
@@ -237,7 +299,8 @@ __device__ __forceinline__ uint32_t encode_chunk(const uint8_t* __restrict__ src
       }
 #pragma unroll
       for (uint32_t r = 0; r < kRows; ++r) {
-        const Z raw = z[r];
+        const Z raw = row_in<T>(x, z[r]);
+        z[r] = raw;
         uint32_t width_here;
         if (E == 1) {
           if (DELTA) {
@@ -271,7 +334,7 @@ __device__ __forceinline__ uint32_t encode_chunk(const uint8_t* __restrict__ src
         before = last_lane<Z>(raw);
         const uint32_t w = wave::reduce_max(width_here);
         widths = lane == r ? w : widths;
-        if (E > 1 && DELTA) {
+        if (E > 1 && (DELTA || !X::kIdentity)) {
           wave::sched_fence(); /* (the rows' E-element bodies interleaved: 100 spilled registers for one-byte elements) */
         }
       }
@@ -284,9 +347,9 @@ __device__ __forceinline__ uint32_t encode_chunk(const uint8_t* __restrict__ src
           uint32_t width_here = 0;
           if (E == 1) {
             if (i < nelem) {
-              const T e = load_elem<T>(src + (size_t)i * S);
+              const T e = x.template in<T>(load_elem<T>(src + (size_t)i * S));
               if (DELTA) {
-                const T prev = i ? load_elem<T>(src + (size_t)(i - 1) * S) : (T)0;
+                const T prev = i ? x.template in<T>(load_elem<T>(src + (size_t)(i - 1) * S)) : (T)0;
                 z[r] = (Z)zigzag<T>((T)(e - prev));
               } else {
                 z[r] = (Z)e;
@@ -297,10 +360,10 @@ __device__ __forceinline__ uint32_t encode_chunk(const uint8_t* __restrict__ src
             /* E elements from one dword; their predecessors from the dword one element earlier */
             uint32_t packed = 0;
             if (i + E <= nelem) {
-              const uint32_t v = load_elem<uint32_t>(src + (size_t)i * S);
+              const uint32_t v = (uint32_t)row_in<T>(x, (Z)load_elem<uint32_t>(src + (size_t)i * S));
               uint32_t pv = 0;
               if (DELTA) {
-                pv = i ? load_elem<uint32_t>(src + (size_t)(i - 1) * S) : v << (8 * S);
+                pv = i ? (uint32_t)row_in<T>(x, (Z)load_elem<uint32_t>(src + (size_t)(i - 1) * S)) : v << (8 * S);
               }
 #pragma unroll
               for (uint32_t k = 0; k < E; ++k) {
@@ -312,8 +375,8 @@ __device__ __forceinline__ uint32_t encode_chunk(const uint8_t* __restrict__ src
 #pragma unroll
               for (uint32_t k = 0; k < E; ++k) {
                 if (i + k < nelem) {
-                  const T e = load_elem<T>(src + (size_t)(i + k) * S);
-                  const T prev = (DELTA && i + k) ? load_elem<T>(src + (size_t)(i + k - 1) * S) : (T)0;
+                  const T e = x.template in<T>(load_elem<T>(src + (size_t)(i + k) * S));
+                  const T prev = (DELTA && i + k) ? x.template in<T>(load_elem<T>(src + (size_t)(i + k - 1) * S)) : (T)0;
                   const T zz = DELTA ? zigzag<T>((T)(e - prev)) : e;
                   packed |= (uint32_t)zz << (8 * S * k);
                 }
@@ -381,9 +444,9 @@ __device__ __forceinline__ uint32_t encode_chunk(const uint8_t* __restrict__ src
 
 /* ---- decompress ---------------------------------------------------------------- */
 
-template <class T, bool DELTA, bool CHECKED>
+template <class T, bool DELTA, bool CHECKED, class X = AsIs>
 __device__ __forceinline__ uint32_t decode_body(
-    const uint8_t* __restrict__ in, uint32_t in_len, uint8_t* __restrict__ out, uint32_t n, uint32_t& err)
+    const uint8_t* __restrict__ in, uint32_t in_len, uint8_t* __restrict__ out, uint32_t n, uint32_t& err, const X x = X())
 {
   constexpr uint32_t S = sizeof(T);
   constexpr uint32_t W = 8 * S;
@@ -471,8 +534,8 @@ __device__ __forceinline__ uint32_t decode_body(
             e = incl;
           }
           const uint32_t i = base + 64 * row + lane;
-          if (i < nelem) {
-            store_elem<T>(out + (size_t)i * S, e);
+          if (i < nelem && x.keep(i)) {
+            store_elem<T>(out + (size_t)i * S, x.template out<T>(e));
           }
         } else if (E == 1) {
           const T v = (T)bits;
@@ -483,8 +546,8 @@ __device__ __forceinline__ uint32_t decode_body(
             e = incl;
           }
           const uint32_t i = base + 64 * row + lane;
-          if (i < nelem) {
-            store_elem<T>(out + (size_t)i * S, e);
+          if (i < nelem && x.keep(i)) {
+            store_elem<T>(out + (size_t)i * S, x.template out<T>(e));
           }
         } else {
           held |= bits << (8 * S * part);
@@ -514,12 +577,13 @@ __device__ __forceinline__ uint32_t decode_body(
             carry = (T)(wave::read_lane(incl, 63) + (uint32_t)carry);
           }
           const uint32_t i = base + kRowElems * row + E * lane;
-          if (i + E <= nelem) {
+          vals = (uint32_t)row_out<T>(x, (typename PackedRow<T>::type)vals);
+          if (i + E <= nelem && x.keep(i) && x.keep(i + E - 1)) {
             store_elem<uint32_t>(out + (size_t)i * S, vals);
           } else {
 #pragma unroll
             for (uint32_t k = 0; k < E; ++k) {
-              if (i + k < nelem) {
+              if (i + k < nelem && x.keep(i + k)) {
                 store_elem<T>(out + (size_t)(i + k) * S, (T)(vals >> (8 * S * k)));
               }
             }

@@ -72,7 +72,9 @@ struct nvcompManagerBase
   virtual void compress(const uint8_t* decomp_buffer, uint8_t* comp_buffer, const CompressionConfig& comp_config) = 0;
   /* reads the container header: synchronises the stream (doc/highlevel_cpp_quickstart.md:113-115) */
   virtual DecompressionConfig configure_decompression(const uint8_t* comp_buffer) = 0;
-  /* no synchronisation: sizes come from the compression configuration */
+  /* no synchronisation: sizes come from the compression configuration. The header is not read here, so a
+   * ComputeAndVerify manager cannot refuse a buffer without checksums the way the overload above does: decompress()
+   * then verifies nothing and reports nvcompSuccess (tests/test_hlif_managers.py pins this) */
   virtual DecompressionConfig configure_decompression(const CompressionConfig& comp_config) = 0;
   virtual void decompress(uint8_t* decomp_buffer, const uint8_t* comp_buffer, const DecompressionConfig& decomp_config) = 0;
   /* synchronises the stream and returns the size the last compress() produced */

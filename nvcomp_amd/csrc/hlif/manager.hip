@@ -15,6 +15,11 @@
  *            u64 comp_offset[N+1] start of every chunk relative to the data area (8-byte aligned)
  *            u32 crc_uncomp[N], u32 crc_comp[N]   (only when checksums were computed)
  *   then     the compressed chunks, each starting on an 8-byte boundary.
+ *
+ * The container is a function of the input and the manager's settings alone: the up to 7 padding bytes behind a chunk
+ * are zero, and so are both checksum tables when no checksums were computed. decompress() confines every chunk to the
+ * data area [0, comp_offset[N]), which itself has to fit into the header's total container size: a table entry that
+ * points anywhere else is decoded as an empty chunk, i.e. nvcompErrorCannotDecompress, and never dereferenced.
  */
 #include <hip/hip_runtime.h>
 
@@ -206,11 +211,25 @@ __global__ void __launch_bounds__(256) layout_kernel(
   }
   __syncthreads();
   uint64_t run = partial[threadIdx.x];
+  /* without checksums nobody else writes their slots: they are zero, not whatever the caller's buffer held */
+  uint32_t* crc_u = (uint32_t*)(offsets + n + 1);
+  const bool no_sums = !(header.flags & kFlagChecksums);
   for (size_t i = lo; i < hi; ++i) {
     offsets[i] = run;
     sizes_out[i] = comp_sizes[i];
     run += (comp_sizes[i] + 7) & ~(uint64_t)7;
+    if (no_sums) {
+      crc_u[i] = 0;
+      crc_u[n + i] = 0;
+    }
   }
+}
+
+/* The 8-byte word at offset `o` of a chunk of `size` bytes: what lies behind the chunk's last byte (staging memory that
+ * earlier calls have used) becomes zero. o < round8(size). */
+__device__ __forceinline__ uint64_t keep_chunk_bytes(uint64_t word, size_t o, size_t size)
+{
+  return o + 8 > size ? word & ((1ull << (8 * (size - o))) - 1) : word;
 }
 
 /* One wavefront per chunk: staged chunk -> its final place in the container. */
@@ -225,21 +244,27 @@ __global__ void __launch_bounds__(256) gather_kernel(const uint8_t* stage, size_
   const uint64_t* offsets = sizes + n;
   const uint8_t* src = stage + i * stride; /* both sides are 8-byte aligned */
   uint8_t* dst = comp_buffer + sizeof(Header) + tables + offsets[i];
-  const size_t bytes = (sizes[i] + 7) / 8 * 8;
+  const size_t size = sizes[i];
+  const size_t bytes = (size + 7) / 8 * 8;
   /* 16 bytes per lane, four loads of 1 KiB in flight before the first store (8 bytes per lane, one load -> store round
    * trip per 512 bytes, took 270 microseconds per GiB of input: 2.6 % of an LZ4 manager's compress()) */
   size_t at = 0;
   for (; at + 4096 <= bytes; at += 4096) {
     const size_t o = at + 16 * lane;
     const wave::u32x4 a = wave::gload_u32x4(src + o), b = wave::gload_u32x4(src + o + 1024);
-    const wave::u32x4 c = wave::gload_u32x4(src + o + 2048), d = wave::gload_u32x4(src + o + 3072);
+    const wave::u32x4 c = wave::gload_u32x4(src + o + 2048);
+    wave::u32x4 d = wave::gload_u32x4(src + o + 3072);
+    /* the chunk's last word, if it is in this step, is the upper half of the last lane's `d` */
+    const uint64_t last = keep_chunk_bytes((uint64_t)d.z | (uint64_t)d.w << 32, o + 3072 + 8, size);
+    d.z = (uint32_t)last;
+    d.w = (uint32_t)(last >> 32);
     wave::gstore_u32x4(dst + o, a);
     wave::gstore_u32x4(dst + o + 1024, b);
     wave::gstore_u32x4(dst + o + 2048, c);
     wave::gstore_u32x4(dst + o + 3072, d);
   }
   for (size_t o = at + 8 * lane; o < bytes; o += 512) {
-    *(uint64_t*)(dst + o) = *(const uint64_t*)(src + o);
+    *(uint64_t*)(dst + o) = keep_chunk_bytes(*(const uint64_t*)(src + o), o, size);
   }
 }
 
@@ -251,8 +276,17 @@ __global__ void setup_decompress_kernel(
   if (i < n) {
     const uint64_t* sizes = (const uint64_t*)(comp_buffer + sizeof(Header));
     const uint64_t* offsets = sizes + n;
-    comp_ptrs[i] = comp_buffer + sizeof(Header) + tables + offsets[i];
-    comp_sizes[i] = sizes[i];
+    /* The tables are input like the chunks: a chunk lies inside the data area [0, offsets[n]), and the data area inside
+     * the container the header declares. An entry that does not is handed on as an empty chunk at the start of the data
+     * area: the decoder reports it, nothing (the checksum kernel included) reads where it pointed. */
+    const uint64_t declared = ((const Header*)comp_buffer)->compressed_size;
+    const uint64_t front = sizeof(Header) + tables;
+    const uint64_t room = declared > front ? declared - front : 0;
+    const uint64_t area = offsets[n] < room ? offsets[n] : room;
+    const uint64_t off = offsets[i], size = sizes[i];
+    const bool inside = off <= area && size <= area - off;
+    comp_ptrs[i] = comp_buffer + front + (inside ? off : 0);
+    comp_sizes[i] = inside ? size : 0;
     /* never past the end of the buffer, whatever the configuration claims */
     const size_t lo = i * chunk < total ? i * chunk : total;
     out_ptrs[i] = decomp + lo;

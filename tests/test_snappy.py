@@ -403,16 +403,10 @@ def test_compress_small_chunk_at_the_end_of_a_mapping(emu, oracle, fmt):
     matches from 8 bytes on). On the emulator the kernels are host code: chunks of 1 .. 16 bytes that END on the last byte in
     front of a PROT_NONE page are compressed in place -- a read past the end is a segfault."""
     import ctypes as C
-    import mmap
 
-    libc = C.CDLL(None, use_errno=True)
-    libc.mmap.restype = C.c_void_p
-    libc.mmap.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_long]
-    libc.mprotect.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
-    page = mmap.PAGESIZE
-    base = libc.mmap(None, 2 * page, mmap.PROT_READ | mmap.PROT_WRITE, mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS, -1, 0)
-    assert base not in (None, C.c_void_p(-1).value)
-    assert libc.mprotect(base + page, page, 0) == 0  # PROT_NONE
+    from hlif_container import guarded_mapping
+
+    base, page = guarded_mapping(1)  # one page, PROT_NONE behind it
     codec = emu.codec(fmt)
     lib = emu.lib
     sizes = list(range(1, 17))
@@ -442,17 +436,10 @@ def test_compress_runs_at_the_end_of_a_mapping(emu, oracle, fmt):
     it): chunks of runs whose last byte is the last one in front of a PROT_NONE page, sizes around the 1 KiB steps and the
     16-byte lanes."""
     import ctypes as C
-    import mmap
 
-    libc = C.CDLL(None, use_errno=True)
-    libc.mmap.restype = C.c_void_p
-    libc.mmap.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_long]
-    libc.mprotect.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
-    page = mmap.PAGESIZE
-    span = 20 * page
-    base = libc.mmap(None, span + page, mmap.PROT_READ | mmap.PROT_WRITE, mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS, -1, 0)
-    assert base not in (None, C.c_void_p(-1).value)
-    assert libc.mprotect(base + span, page, 0) == 0  # PROT_NONE behind the chunk
+    from hlif_container import guarded_mapping
+
+    base, span = guarded_mapping(20)  # PROT_NONE behind the chunk
     codec = emu.codec(fmt)
     lib = emu.lib
     for n in (4096, 4097, 4111, 4112, 4113, 5119, 5120, 5121, 8191, 65535, 65536):

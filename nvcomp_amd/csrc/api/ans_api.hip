@@ -7,13 +7,12 @@
 
 #include "nvcomp/ans.h"
 
+#include "common/api_launch.h"
 #include "common/log.h"
 
 #include "ans/ans.hip.h"
 
 namespace {
-
-constexpr unsigned kWavesPerBlock = 4;
 
 __global__ void __launch_bounds__(64 * kWavesPerBlock) ans_compress_kernel(
     const void* const* __restrict__ in_ptrs,
@@ -92,21 +91,6 @@ __global__ void __launch_bounds__(256) ans_decompress_size_kernel(
     n = ans::load_as<uint32_t>(in + 4);
   }
   out_bytes[chunk] = n;
-}
-
-void clear_stale_error()
-{
-  (void)hipGetLastError();
-}
-
-nvcompStatus_t launch_status()
-{
-  return hipGetLastError() == hipSuccess ? nvcompSuccess : nvcompErrorCudaError;
-}
-
-unsigned grid_for(size_t batch_size)
-{
-  return (unsigned)((batch_size + kWavesPerBlock - 1) / kWavesPerBlock);
 }
 
 bool opts_ok(nvcompBatchedANSOpts_t o)

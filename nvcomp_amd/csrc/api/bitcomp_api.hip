@@ -7,13 +7,13 @@
 
 #include "nvcomp/bitcomp.h"
 
+#include "common/api_launch.h"
 #include "common/log.h"
 
 #include "bitcomp/bitcomp.hip.h"
 
 namespace {
 
-constexpr unsigned kWavesPerBlock = 4;
 constexpr uint32_t kMaxOutCap = 1u << 26;
 
 /* Workgroups per CU the register allocation aims at: 8 (64 registers) spills 12-20 registers of the 8-byte element types,
@@ -97,21 +97,6 @@ __global__ void __launch_bounds__(256) bitcomp_decompress_size_kernel(
     n = bitcomp::load_u32(in + 8);
   }
   out_bytes[chunk] = n;
-}
-
-void clear_stale_error()
-{
-  (void)hipGetLastError();
-}
-
-nvcompStatus_t launch_status()
-{
-  return hipGetLastError() == hipSuccess ? nvcompSuccess : nvcompErrorCudaError;
-}
-
-unsigned grid_for(size_t batch_size)
-{
-  return (unsigned)((batch_size + kWavesPerBlock - 1) / kWavesPerBlock);
 }
 
 /* element size for a type code, 0 when the code is not a Bitcomp type */

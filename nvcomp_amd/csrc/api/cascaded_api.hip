@@ -10,6 +10,7 @@
 
 #include "nvcomp/cascaded.h"
 
+#include "common/api_launch.h"
 #include "common/log.h"
 
 #include "cascaded/cascaded.hip.h"
@@ -63,16 +64,6 @@ constexpr uint32_t kBigBudget = 64 * 1024;        /* last pass: one wave per wor
 #endif
 constexpr size_t kCus = NVCOMP_CASC_CUS;
 constexpr size_t kLdsPerCu = 160 * 1024;
-
-void clear_stale_error()
-{
-  (void)hipGetLastError();
-}
-
-nvcompStatus_t launch_status()
-{
-  return hipGetLastError() == hipSuccess ? nvcompSuccess : nvcompErrorCudaError;
-}
 
 bool opts_ok(const nvcompBatchedCascadedOpts_t& o)
 {
@@ -682,18 +673,6 @@ nvcompStatus_t nvcompBatchedCascadedDecompressGetTempSizeEx(
 /* Profiling builds only: read (and clear) the per-phase cycle sums of the Cascaded decoder. */
 extern "C" int nvcompAmdCascProfRead(unsigned long long* host_slots, int n)
 {
-  static unsigned long long v[casc::kProfSlots * 64];
-  if (hipMemcpyFromSymbol(v, HIP_SYMBOL(casc::g_prof), sizeof(v)) != hipSuccess) {
-    return -1;
-  }
-  for (int i = 0; i < n && i < (int)casc::kProfSlots; ++i) {
-    host_slots[i] = 0;
-    for (int k = 0; k < 64; ++k) {
-      host_slots[i] += v[i * 64 + k];
-    }
-  }
-  static const unsigned long long z[casc::kProfSlots * 64] = {};
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(casc::g_prof), z, sizeof(z));
-  return (int)casc::kProfSlots;
+  return prof_read_and_clear<casc::kProfSlots, 64>(casc::g_prof, host_slots, n); /* 64 copies of every slot */
 }
 #endif

@@ -17,6 +17,7 @@
 
 #include "nvcomp/crc32.h"
 
+#include "common/api_launch.h"
 #include "common/log.h"
 #include "common/lz_launch.hip.h"
 #include "common/wave.h"
@@ -92,18 +93,6 @@ __global__ void __launch_bounds__(64 * kWavesPerGroup) crc32_kernel(
       atomic_xor(&out[i], r);
     }
   }
-}
-
-/* hipGetLastError() is sticky per host thread: an unrelated earlier runtime call of the application must not be
- * reported as this launch's failure, so the slate is cleared before launching. */
-void clear_stale_error()
-{
-  (void)hipGetLastError();
-}
-
-nvcompStatus_t launch_status()
-{
-  return hipGetLastError() == hipSuccess ? nvcompSuccess : nvcompErrorCudaError;
 }
 
 } // namespace

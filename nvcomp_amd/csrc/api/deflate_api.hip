@@ -10,6 +10,7 @@
 #include "nvcomp/deflate.h"
 #include "nvcomp/gzip.h"
 
+#include "common/api_launch.h"
 #include "common/log.h"
 
 #include "deflate/deflate_decode.hip.h"
@@ -144,18 +145,6 @@ __global__ void __launch_bounds__(64 * kEncWaves, DYNAMIC ? 3 : 4) deflate_compr
   if (wave::lane_id() == 0) {
     out_bytes[chunk] = produced;
   }
-}
-
-/* hipGetLastError() is sticky per host thread: an unrelated earlier runtime call of the application must not be
- * reported as this launch's failure, so the slate is cleared before launching. */
-void clear_stale_error()
-{
-  (void)hipGetLastError();
-}
-
-nvcompStatus_t launch_status()
-{
-  return hipGetLastError() == hipSuccess ? nvcompSuccess : nvcompErrorCudaError;
 }
 
 bool deflate_opts_ok(nvcompBatchedDeflateOpts_t opts)
@@ -380,15 +369,6 @@ nvcompStatus_t nvcompBatchedDeflateCompressAsync(
  * 1 = window tables, 2 = enumerations, 3 = a round's decode + records, 10 = symbols decoded one at a time, 15 = the rest. */
 extern "C" int nvcompAmdProfReadDeflate(unsigned long long* host_slots, int n)
 {
-  unsigned long long v[lzw::kProfSlots] = {};
-  if (hipMemcpyFromSymbol(v, HIP_SYMBOL(lzw::g_prof), sizeof(v)) != hipSuccess) {
-    return -1;
-  }
-  for (int i = 0; i < n && i < (int)lzw::kProfSlots; ++i) {
-    host_slots[i] = v[i];
-  }
-  unsigned long long z[lzw::kProfSlots] = {};
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(lzw::g_prof), z, sizeof(z));
-  return (int)lzw::kProfSlots;
+  return prof_read_and_clear<lzw::kProfSlots>(lzw::g_prof, host_slots, n);
 }
 #endif

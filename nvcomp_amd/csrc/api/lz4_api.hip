@@ -2,6 +2,7 @@
  * api/lz4_api.hip -- C ABI of the batched LZ4 codec (include/nvcomp/lz4.h) and
  * the kernels it launches. Host side does argument checks and one launch per
  * *Async call on the caller's stream; nothing here allocates or synchronises.
+ * What LZ4 shares with Snappy (kernel bodies, launches, dispatch) is common/lz_api.hip.h.
  */
 #include <hip/hip_runtime.h>
 
@@ -9,39 +10,19 @@
 
 #include "nvcomp/lz4.h"
 
-#include "common/log.h"
-
 #include "nvcomp/amd_ext.h"
 
-#include "common/lz_launch.hip.h"
+#include "common/lz_api.hip.h"
 #include "lz4/lz4_decode.hip.h"
 #include "lz4/lz4_decode_window.hip.h"
-#include "common/lz_team.hip.h"
 #include "lz4/lz4_encode.hip.h"
 
 namespace {
 
-constexpr unsigned kWavesPerBlock = 4; /* 256-thread workgroups, one chunk per wave */
-#ifndef NVCOMP_LZ_DEC_WAVES_PER_BLOCK
-#define NVCOMP_LZ_DEC_WAVES_PER_BLOCK 4
-#endif
-constexpr unsigned kDecWaves = NVCOMP_LZ_DEC_WAVES_PER_BLOCK;
-#ifndef NVCOMP_LZM_WAVES_PER_BLOCK
-#define NVCOMP_LZM_WAVES_PER_BLOCK 4
-#endif
-constexpr unsigned kEncWaves = NVCOMP_LZM_WAVES_PER_BLOCK; /* the compressors' workgroup size */
-/* Untyped data takes the 256-position steps of common/lz_match_wide.hip.h (0: the one-window compressor, A/B build). */
-#ifndef NVCOMP_LZM_WIDE
-#define NVCOMP_LZM_WIDE 1
-#endif
-#ifndef NVCOMP_LZMW_WAVES_PER_BLOCK
-#define NVCOMP_LZMW_WAVES_PER_BLOCK 1
-#endif
-constexpr unsigned kWideWaves = NVCOMP_LZMW_WAVES_PER_BLOCK;
-#ifndef NVCOMP_LZMW_WAVES_PER_SIMD
-#define NVCOMP_LZMW_WAVES_PER_SIMD 4 /* what the wave's LDS allows (15-16 waves per CU): a budget of 128 registers */
-#endif
-using lzl::kMaxOutCap;
+using lzl::kDecWaves;
+using lzl::kEncWaves;
+using lzl::kWideWaves;
+
 #ifndef NVCOMP_LZ4_PAIR_RUNS
 #define NVCOMP_LZ4_PAIR_RUNS 0 /* the two-wave kernel's consumer with the run executor (A/B) */
 #endif
@@ -64,200 +45,63 @@ static_assert(lzl::kIndexBytesPerWave >= lzx::kScratchPerWave, "a wave's slice o
 #define NVCOMP_LZ4W_ABLATE 0
 #endif
 
-/* Decode chunk `chunk` of the batch with the calling wave and report its size and status. */
-template <bool CHECKED, class BatchPtr>
-__device__ __forceinline__ void decode_one(BatchPtr b, size_t chunk, uint8_t* lds, uint8_t* index_scratch)
+/* LZ4 as common/lz_api.hip.h sees it. */
+struct Lz4
 {
-  const uint8_t* in = wave::uniform_ptr((const uint8_t*)b->comp_ptrs[chunk]);
-  uint8_t* out = wave::uniform_ptr((uint8_t*)b->out_ptrs[chunk]);
-  const size_t in_len64 = wave::uniform64(b->comp_bytes[chunk]);
-  size_t cap64 = wave::uniform64(b->out_caps[chunk]);
-  if (cap64 > kMaxOutCap) {
-    cap64 = kMaxOutCap;
+  using TeamFrontEnd = lz4w::TeamFrontEnd;
+  static constexpr bool kEmptyIsError = false;
+  /* a chunk that shrank 8 x or more (by the caller's capacity: an LZ4 block does not say what it decodes to) takes the
+   * instance of the loop that tries the run executor; everything else the one without it (lz4w::decode_chunk) */
+  static __device__ __forceinline__ bool runs(size_t in_len, size_t cap) { return NVCOMP_LZW_RUNS && in_len * kRunsRatio <= cap; }
+  template <bool CHECKED>
+  static __device__ __forceinline__ uint32_t alone(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint8_t* lds, uint32_t& err)
+  {
+    return lz4w::decode_chunk<CHECKED, 0, true>(in, n, out, cap, lds, err, nullptr);
   }
-  uint32_t err = lz::kErrNone;
-  uint32_t produced = 0;
-  if (in_len64 > 0xffffffffull - 64) {
-    err = lz::kErrInput;
-  } else {
-    /* a chunk that shrank 8 x or more (by the caller's capacity: an LZ4 block does not say what it decodes to) takes the
-     * instance of the loop that tries the run executor; everything else the one without it (lz4w::decode_chunk) */
-    if (NVCOMP_LZW_RUNS && in_len64 * kRunsRatio <= cap64) {
-      produced = lz4w::decode_chunk<CHECKED, NVCOMP_LZ4W_ABLATE, true>(in, (uint32_t)in_len64, out, (uint32_t)cap64, lds, err, index_scratch);
-    } else {
-      produced = lz4w::decode_chunk<CHECKED, NVCOMP_LZ4W_ABLATE, false>(in, (uint32_t)in_len64, out, (uint32_t)cap64, lds, err, index_scratch);
-    }
+  template <bool CHECKED>
+  static __device__ __forceinline__ void produce(const uint8_t* in, uint32_t n, uint8_t* lds)
+  {
+    lz4w::pair::produce(in, n, lds);
   }
-  if (wave::lane_id() == 0) {
-    size_t* actual_bytes = b->actual_bytes;
-    if (actual_bytes != nullptr) {
-      actual_bytes[chunk] = err ? 0 : produced;
-    }
-    if (CHECKED && b->statuses != nullptr) {
-      b->statuses[chunk] = err ? nvcompErrorCannotDecompress : nvcompSuccess;
-    }
+  template <bool CHECKED, bool TEAM>
+  static __device__ __forceinline__ uint32_t consume(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint8_t* lds, uint32_t& err)
+  {
+    return lz4w::pair::consume<CHECKED, !TEAM && NVCOMP_LZ4_PAIR_RUNS != 0>(in, n, out, cap, lds, err);
   }
-}
+};
 
-/* One wave per chunk at a time; with a ticket counter the waves are persistent (common/lz_launch.hip.h). */
 template <bool CHECKED>
 __global__ void __launch_bounds__(64 * kDecWaves, NVCOMP_LZW_WAVES_PER_SIMD) lz4_decompress_window_kernel(const lzl::Launch launch)
 {
   __shared__ __attribute__((aligned(16))) uint8_t lds[kDecWaves][lzw::kLdsPerWave];
   const uint32_t w = wave::uniform(threadIdx.x >> 6);
-  size_t place = (size_t)blockIdx.x * kDecWaves + w; /* the wave's place in the launch = its first chunk */
-#ifdef NVCOMP_LZW_PROF
-  lzw::prof_begin();
-#endif
-  for (;;) {
-    /* the arguments are read where they are used, not held in scalar registers across the decode (wave::kernel_args) */
-    const auto* a = wave::kernel_args(launch);
-    if (place >= a->b.batch_size) {
-      break;
-    }
-    const size_t chunk = place;
+  lzl::decode_window_loop<CHECKED>(launch, w, [&](const lzl::Chunk& c, const auto* a, uint32_t& err) -> uint32_t {
     /* the wave's slice of the temp buffer for the token index (the same for every chunk it decodes) */
     uint8_t* index = a->index;
     if (index != nullptr) {
       index += ((size_t)blockIdx.x * kDecWaves + w) * lzl::kIndexBytesPerWave;
     }
-    decode_one<CHECKED>(&a->b, chunk, lds[w], index);
-    a = wave::kernel_args(launch);
-    uint32_t* ticket = a->ticket;
-    if (ticket == nullptr) {
-      break;
+    if (Lz4::runs(c.in_len, c.cap)) {
+      return lz4w::decode_chunk<CHECKED, NVCOMP_LZ4W_ABLATE, true>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err, index);
     }
-    place = lzl::next_chunk(ticket, a->first_dynamic);
-  }
-#ifdef NVCOMP_LZW_PROF
-  lzw::prof_end();
-#endif
+    return lz4w::decode_chunk<CHECKED, NVCOMP_LZ4W_ABLATE, false>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err, index);
+  });
 }
 
-/* Small batches: two waves per chunk, a producer (chase + parse) and a consumer (execute), lz4w::pair. */
 template <bool CHECKED>
 __global__ void __launch_bounds__(128, 7) lz4_decompress_pair_kernel(const lzl::Batch b)
 {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[lz4w::pair::kLdsPerChunk];
-  const uint32_t w = wave::uniform(threadIdx.x >> 6);
-  const size_t chunk = blockIdx.x;
-  if (chunk >= b.batch_size) {
-    return;
-  }
-  if (threadIdx.x < 4) {
-    ((uint32_t*)(lds + lz4w::pair::kLdsPerChunk - lz4w::pair::kCtrlBytes))[threadIdx.x] = 0; /* both slots empty, no abort */
-  }
-  __syncthreads();
-  const uint8_t* in = wave::uniform_ptr((const uint8_t*)b.comp_ptrs[chunk]);
-  uint8_t* out = wave::uniform_ptr((uint8_t*)b.out_ptrs[chunk]);
-  const size_t in_len64 = wave::uniform64(b.comp_bytes[chunk]);
-  size_t cap64 = wave::uniform64(b.out_caps[chunk]);
-  if (cap64 > kMaxOutCap) {
-    cap64 = kMaxOutCap;
-  }
-  const bool too_long = in_len64 > 0xffffffffull - 64;
-  const bool work = !too_long && in_len64 != 0;
-  /* A chunk that shrank 8 x or more is decoded by the second wave ALONE, with the one-wave loop that holds the run
-   * executor (lz4w::decode_chunk<., ., true>; the first wave leaves): sorted keys and typed columns are 4-5 x faster there
-   * than through producer and consumer (4 096 chunks of the sorted-key column: 840 GB/s here, 5 120 chunks in the
-   * persistent kernel: 3 850). That loop's registers cost this kernel its eighth wave per SIMD (common/lz_launch.hip.h:
-   * the mix does not mind). */
-  static_assert(lzw::kLdsPerWave <= lz4w::pair::kLdsPerChunk, "the lone wave's LDS is the pair's");
-  const bool solo = NVCOMP_LZW_RUNS && NVCOMP_LZ_PAIR_SOLO && work && in_len64 * kRunsRatio <= cap64;
-  if (w == 0) {
-    if (work && !solo) {
-      lz4w::pair::produce(in, (uint32_t)in_len64, lds);
-    }
-    return;
-  }
-  uint32_t err = too_long ? lz::kErrInput : lz::kErrNone;
-  uint32_t produced = 0;
-  if (solo) {
-    produced = lz4w::decode_chunk<CHECKED, 0, true>(in, (uint32_t)in_len64, out, (uint32_t)cap64, lds, err, nullptr);
-  } else if (work) {
-    produced = lz4w::pair::consume<CHECKED, NVCOMP_LZ4_PAIR_RUNS != 0>(in, (uint32_t)in_len64, out, (uint32_t)cap64, lds, err);
-  }
-  if (wave::lane_id() == 0) {
-    if (b.actual_bytes != nullptr) {
-      b.actual_bytes[chunk] = err ? 0 : produced;
-    }
-    if (CHECKED && b.statuses != nullptr) {
-      b.statuses[chunk] = err ? nvcompErrorCannotDecompress : nvcompSuccess;
-    }
-  }
+  __shared__ __attribute__((aligned(16))) uint8_t lds[lzw::pair::kLdsPerChunk];
+  lzl::decode_pair<CHECKED, Lz4>(b, lds);
 }
 
-/* A workgroup per chunk (common/lz_team.hip.h): batches that cannot fill the card with one wave per chunk. Persistent
- * workgroups when the caller's temp buffer holds a ticket counter, one workgroup per chunk otherwise. */
 template <bool CHECKED, uint32_t WAVES>
 __global__ void __launch_bounds__(64 * WAVES, 4) lz4_decompress_team_kernel(const lzl::Launch launch)
 {
   __shared__ __attribute__((aligned(16))) uint8_t lds[lzt::Geo<WAVES>::kLds];
-  size_t chunk = blockIdx.x;
-#ifdef NVCOMP_LZW_PROF
-  lzw::prof_begin();
-#endif
-  for (;;) {
-    const auto* a = wave::kernel_args(launch);
-    if (chunk >= a->b.batch_size) {
-      break;
-    }
-    const uint8_t* in = wave::uniform_ptr((const uint8_t*)a->b.comp_ptrs[chunk]);
-    uint8_t* out = wave::uniform_ptr((uint8_t*)a->b.out_ptrs[chunk]);
-    const size_t in_len64 = wave::uniform64(a->b.comp_bytes[chunk]);
-    size_t cap64 = wave::uniform64(a->b.out_caps[chunk]);
-    if (cap64 > kMaxOutCap) {
-      cap64 = kMaxOutCap;
-    }
-    uint32_t err = lz::kErrNone;
-    uint32_t produced = 0;
-    if (in_len64 > 0xffffffffull - 64) {
-      err = lz::kErrInput;
-    } else {
-      produced = lzt::decode_chunk<lz4w::TeamFrontEnd, WAVES>(
-          in, (uint32_t)in_len64, out, (uint32_t)cap64, lds, err,
-          [](uint32_t role, const uint8_t* i, uint32_t n, uint8_t* o, uint32_t cap, uint8_t* scratch, uint32_t& e) -> uint32_t {
-            /* chunks that shrank 8 x (here: mostly the 16 x ones of the team's own test): runs -- one wave with the loop that
-             * holds the run executor, as in the two-wave kernel */
-            const bool solo = NVCOMP_LZW_RUNS && NVCOMP_LZ_PAIR_SOLO && (size_t)n * kRunsRatio <= cap;
-            if (role == 0) {
-              if (!solo) {
-                lz4w::pair::produce(i, n, scratch);
-              }
-              return 0u;
-            }
-            if (solo) {
-              return lz4w::decode_chunk<true, 0, true>(i, n, o, cap, scratch, e, nullptr);
-            }
-            return lz4w::pair::consume<true, false>(i, n, o, cap, scratch, e);
-          });
-    }
-    a = wave::kernel_args(launch);
-    if (threadIdx.x == 0) {
-      size_t* actual_bytes = a->b.actual_bytes;
-      if (actual_bytes != nullptr) {
-        actual_bytes[chunk] = err ? 0 : produced;
-      }
-      if (CHECKED && a->b.statuses != nullptr) {
-        a->b.statuses[chunk] = err ? nvcompErrorCannotDecompress : nvcompSuccess;
-      }
-    }
-    uint32_t* ticket = a->ticket;
-    if (ticket == nullptr) {
-      break;
-    }
-    uint32_t* slot = (uint32_t*)(lds + lzt::Geo<WAVES>::kLds - 4 * lzt::kCtlWords) + lzt::kCtlTicket;
-    if (threadIdx.x == 0) {
-      *slot = atomicAdd(ticket, 1u);
-    }
-    __syncthreads();
-    chunk = a->first_dynamic + wave::uniform(*slot);
-    __syncthreads();
-  }
-#ifdef NVCOMP_LZW_PROF
-  lzw::prof_end();
-#endif
+  lzl::decode_team_loop<CHECKED, WAVES, Lz4>(launch, lds);
 }
+
 
 /* Inspection (include/nvcomp/amd_ext.h): the token index of every chunk, one wave each. */
 __global__ void __launch_bounds__(64) lz4_token_index_kernel(
@@ -301,20 +145,11 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) lz4_decompress_size_kerne
     size_t* uncompressed_bytes,
     size_t batch_size)
 {
-  const size_t chunk = (size_t)blockIdx.x * kWavesPerBlock + wave::uniform(threadIdx.x >> 6);
-  if (chunk >= batch_size) {
-    return;
-  }
-  const uint8_t* in = wave::uniform_ptr((const uint8_t*)comp_ptrs[chunk]);
-  const size_t in_len64 = wave::uniform64(comp_bytes[chunk]);
-  uint32_t err = lz::kErrNone;
-  uint32_t produced = 0;
-  if (in_len64 <= 0xffffffffull - 8) {
-    produced = lz4::decode_chunk<false, true, true>(in, (uint32_t)in_len64, nullptr, 0, err);
-  }
-  if (wave::lane_id() == 0) {
-    uncompressed_bytes[chunk] = err ? 0 : produced;
-  }
+  lzl::decompress_size(comp_ptrs, comp_bytes, uncompressed_bytes, batch_size, [](const uint8_t* in, uint32_t in_len) -> uint32_t {
+    uint32_t err = lz::kErrNone;
+    const uint32_t produced = lz4::decode_chunk<false, true, true>(in, in_len, nullptr, 0, err);
+    return err ? 0 : produced;
+  });
 }
 
 /* STRIDE: the element size the caller declared (nvcompBatchedLZ4Opts_t.data_type): matches are searched at element
@@ -325,29 +160,9 @@ __global__ void __launch_bounds__(64 * kEncWaves, NVCOMP_LZM_WAVES_PER_SIMD) lz4
   __shared__ uint16_t tables[kEncWaves][lzm::kTableU16];
   __shared__ __attribute__((aligned(8))) uint8_t images[kEncWaves][lzm::kImageBytes];
   const uint32_t w = wave::uniform(threadIdx.x >> 6);
-  size_t chunk = (size_t)blockIdx.x * kEncWaves + w;
-  /* persistent waves, as in the decoders (common/lz_launch.hip.h): chunks of a batch compress at very different speeds */
-  for (;;) {
-    const auto* a = wave::kernel_args(launch);
-    if (chunk >= a->batch_size) {
-      break;
-    }
-    const uint8_t* src = wave::uniform_ptr((const uint8_t*)a->in_ptrs[chunk]);
-    uint8_t* dst = wave::uniform_ptr((uint8_t*)a->out_ptrs[chunk]);
-    const size_t n64 = wave::uniform64(a->in_bytes[chunk]);
-    /* a chunk larger than the caller declared would overrun the output slot sized from GetMaxOutputChunkSize: it is
-     * not compressed, its size reads 0 */
-    const uint32_t produced = n64 > a->max_chunk_bytes ? 0u : lz4::encode_chunk<STRIDE>(src, (uint32_t)n64, dst, tables[w], images[w]);
-    a = wave::kernel_args(launch);
-    if (wave::lane_id() == 0) {
-      a->out_bytes[chunk] = produced;
-    }
-    uint32_t* ticket = a->ticket;
-    if (ticket == nullptr) {
-      break;
-    }
-    chunk = lzl::next_chunk(ticket, a->first_dynamic);
-  }
+  lzl::compress_loop<kEncWaves>(launch, w, [&](const uint8_t* src, uint32_t n, uint8_t* dst) -> uint32_t {
+    return lz4::encode_chunk<STRIDE>(src, n, dst, tables[w], images[w]);
+  });
 }
 
 /* Untyped data: 256-position steps (common/lz_match_wide.hip.h); a wave's LDS is lzm::wide::kLdsPerWave bytes. */
@@ -357,44 +172,9 @@ __global__ void __launch_bounds__(64 * kWideWaves, NVCOMP_LZMW_WAVES_PER_SIMD) l
   __shared__ __attribute__((aligned(16))) uint8_t images[kWideWaves][lzm::wide::kImage];
   __shared__ __attribute__((aligned(16))) uint8_t scratch[kWideWaves][lzm::wide::kScratch];
   const uint32_t w = wave::uniform(threadIdx.x >> 6);
-  size_t chunk = (size_t)blockIdx.x * kWideWaves + w;
-  for (;;) {
-    const auto* a = wave::kernel_args(launch);
-    if (chunk >= a->batch_size) {
-      break;
-    }
-    const uint8_t* src = wave::uniform_ptr((const uint8_t*)a->in_ptrs[chunk]);
-    uint8_t* dst = wave::uniform_ptr((uint8_t*)a->out_ptrs[chunk]);
-    const size_t n64 = wave::uniform64(a->in_bytes[chunk]);
-    const uint32_t produced = n64 > a->max_chunk_bytes ? 0u : lz4::encode_chunk_wide(src, (uint32_t)n64, dst, tables[w], images[w], scratch[w]);
-    a = wave::kernel_args(launch);
-    if (wave::lane_id() == 0) {
-      a->out_bytes[chunk] = produced;
-    }
-    uint32_t* ticket = a->ticket;
-    if (ticket == nullptr) {
-      break;
-    }
-    chunk = lzl::next_chunk(ticket, a->first_dynamic);
-  }
-}
-
-/* hipGetLastError() is sticky per host thread: an unrelated earlier runtime call
- * of the application (e.g. a failed pointer-attribute query) must not be
- * reported as this launch's failure, so the slate is cleared before launching. */
-void clear_stale_error()
-{
-  (void)hipGetLastError();
-}
-
-nvcompStatus_t launch_status()
-{
-  return hipGetLastError() == hipSuccess ? nvcompSuccess : nvcompErrorCudaError;
-}
-
-unsigned grid_for(size_t batch_size)
-{
-  return (unsigned)((batch_size + kWavesPerBlock - 1) / kWavesPerBlock);
+  lzl::compress_loop<kWideWaves>(launch, w, [&](const uint8_t* src, uint32_t n, uint8_t* dst) -> uint32_t {
+    return lz4::encode_chunk_wide(src, n, dst, tables[w], images[w], scratch[w]);
+  });
 }
 
 /* worst case of the block format: one length byte per 255 literals + token + slack (== LZ4_compressBound) */
@@ -403,9 +183,11 @@ size_t lz4_bound(size_t n)
   return n + n / 255 + 16;
 }
 
-bool lz4_type_ok(nvcompType_t t)
+nvcompStatus_t lz4_opts_status(nvcompBatchedLZ4Opts_t opts, size_t max_chunk_bytes)
 {
-  return (t >= NVCOMP_TYPE_CHAR && t <= NVCOMP_TYPE_UINT) || t == NVCOMP_TYPE_BITS;
+  const nvcompType_t t = opts.data_type;
+  return lzl::compress_opts_status((t >= NVCOMP_TYPE_CHAR && t <= NVCOMP_TYPE_UINT) || t == NVCOMP_TYPE_BITS, max_chunk_bytes,
+                                   nvcompLZ4CompressionMaxAllowedChunkSize);
 }
 
 } // namespace
@@ -413,15 +195,11 @@ bool lz4_type_ok(nvcompType_t t)
 extern "C" {
 
 nvcompStatus_t nvcompBatchedLZ4DecompressGetTempSize(
-    size_t num_chunks, size_t max_uncompressed_chunk_bytes, size_t* temp_bytes)
+    size_t num_chunks, size_t /*max_uncompressed_chunk_bytes*/, size_t* temp_bytes)
 {
-  if (temp_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
   /* the ticket counter of the persistent waves / workgroups (common/lz_launch.hip.h) */
-  (void)max_uncompressed_chunk_bytes;
-  *temp_bytes = num_chunks == 0 ? 0 : num_chunks > lzl::kPairMaxBatch && NVCOMP_LZ_INDEX ? lzl::index_temp_bytes(num_chunks) : lzl::kTicketBytes;
-  return nvcompSuccess;
+  return lzl::temp_size(num_chunks, temp_bytes,
+                        num_chunks > lzl::kPairMaxBatch && NVCOMP_LZ_INDEX ? lzl::index_temp_bytes(num_chunks) : lzl::kTicketBytes);
 }
 
 nvcompStatus_t nvcompBatchedLZ4DecompressGetTempSizeEx(
@@ -442,71 +220,10 @@ nvcompStatus_t nvcompBatchedLZ4DecompressAsync(
     nvcompStatus_t* device_statuses,
     hipStream_t stream)
 {
-  nvlog::call(3, "nvcompBatchedLZ4DecompressAsync(batch_size=%zu, statuses=%s, actual_sizes=%s, temp_bytes=%zu, stream=%p)",
-              batch_size, device_statuses ? "yes" : "null", device_actual_uncompressed_bytes ? "yes" : "null", temp_bytes,
-              (void*)stream);
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_compressed_ptrs == nullptr || device_compressed_bytes == nullptr || device_uncompressed_bytes == nullptr
-      || device_uncompressed_ptrs == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  /* Bounds are checked whether or not the caller asked for statuses (round 4): the kernels without the checks were no
-   * faster (655-668 against 675 GB/s on the headline batch over three evidence runs: the checks are a handful of
-   * wave-uniform tests per batch), and a corrupt stream decoded with statuses == NULL could write past its output slot.
-   * A NULL status array now only means that nobody is told: a failed chunk still reads 0 in
-   * device_actual_uncompressed_bytes. */
-  (void)device_statuses; /* (only the kernels look at it) */
-  const lzl::Batch b = {device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
-                        device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, (int*)device_statuses};
-  /* Small batches cannot fill the card with one wave per chunk: a workgroup per chunk (common/lz_team.hip.h), persistent
-   * when there are more chunks than workgroups stay resident and the caller's temp buffer holds the ticket counter. */
-  if (batch_size <= lzl::kTeamMaxBatch) {
-    unsigned groups = (unsigned)batch_size;
-    uint32_t* ticket = nullptr;
-    const lzl::Launch one_each = {b, nullptr, (size_t)groups, nullptr};
-    if (batch_size <= lzl::kTeam16MaxBatch) {
-      /* at most one chunk per CU: sixteen waves a chunk (one team holds a whole CU's LDS budget for two) */
-      hipLaunchKernelGGL((lz4_decompress_team_kernel<true, 16>), dim3(groups), dim3(1024), 0, stream, one_each);
-      return launch_status();
-    }
-    if (device_temp_ptr != nullptr && temp_bytes >= sizeof(uint32_t) && ((uintptr_t)device_temp_ptr & 3u) == 0) {
-      static lzl::ResidentCache resident; /* per device ordinal */
-      const unsigned fit = resident.get(lz4_decompress_team_kernel<true, 8>, 512, 0);
-      if (fit != 0 && fit < groups && hipMemsetAsync(device_temp_ptr, 0, sizeof(uint32_t), stream) == hipSuccess) {
-        ticket = (uint32_t*)device_temp_ptr;
-        groups = fit;
-      }
-    }
-    const lzl::Launch launch = {b, ticket, (size_t)groups, nullptr};
-    hipLaunchKernelGGL((lz4_decompress_team_kernel<true, 8>), dim3(groups), dim3(512), 0, stream, launch);
-    return launch_status();
-  }
-  /* (round 2's path for small batches: two waves per chunk, producer / consumer) */
-  if (batch_size <= lzl::kPairMaxBatch) {
-    const dim3 pgrid((unsigned)batch_size), pblock(128);
-    hipLaunchKernelGGL((lz4_decompress_pair_kernel<true>), pgrid, pblock, 0, stream, b);
-    return launch_status();
-  }
-  /* Persistent waves when the caller's temp buffer holds the ticket counter: as many workgroups as stay resident. */
-  unsigned groups = (unsigned)((batch_size + kDecWaves - 1) / kDecWaves);
-  uint32_t* ticket = nullptr;
-#if NVCOMP_LZ_PERSISTENT
-  if (device_temp_ptr != nullptr && temp_bytes >= sizeof(uint32_t) && ((uintptr_t)device_temp_ptr & 3u) == 0) {
-    static lzl::ResidentCache resident; /* per device ordinal */
-    const unsigned fit = resident.get(lz4_decompress_window_kernel<true>, 64 * kDecWaves);
-    if (fit != 0 && fit < groups && hipMemsetAsync(device_temp_ptr, 0, sizeof(uint32_t), stream) == hipSuccess) {
-      ticket = (uint32_t*)device_temp_ptr;
-      groups = fit;
-    }
-  }
-#endif
-  uint8_t* index = NVCOMP_LZ_INDEX ? lzl::index_base(device_temp_ptr, temp_bytes, (size_t)groups * kDecWaves) : nullptr;
-  const lzl::Launch launch = {b, ticket, (size_t)groups * kDecWaves, index};
-  hipLaunchKernelGGL((lz4_decompress_window_kernel<true>), dim3(groups), dim3(64 * kDecWaves), 0, stream, launch);
-  return launch_status();
+  return lzl::decompress_async<lz4_decompress_team_kernel<true, 16>, lz4_decompress_team_kernel<true, 8>,
+                               lz4_decompress_pair_kernel<true>, lz4_decompress_window_kernel<true>>(
+      "LZ4", NVCOMP_LZ_INDEX != 0, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
+      device_actual_uncompressed_bytes, batch_size, device_temp_ptr, temp_bytes, device_uncompressed_ptrs, device_statuses, stream);
 }
 
 nvcompStatus_t nvcompAmdBatchedLZ4TokenIndexAsync(
@@ -536,30 +253,15 @@ nvcompStatus_t nvcompBatchedLZ4GetDecompressSizeAsync(
     size_t batch_size,
     hipStream_t stream)
 {
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_compressed_ptrs == nullptr || device_compressed_bytes == nullptr || device_uncompressed_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  hipLaunchKernelGGL(lz4_decompress_size_kernel, dim3(grid_for(batch_size)), dim3(64 * kWavesPerBlock), 0, stream,
-                     device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes, batch_size);
-  return launch_status();
+  return lzl::decompress_size_async<lz4_decompress_size_kernel>(device_compressed_ptrs, device_compressed_bytes,
+                                                                device_uncompressed_bytes, batch_size, stream);
 }
 
 nvcompStatus_t nvcompBatchedLZ4CompressGetTempSize(
     size_t batch_size, size_t max_uncompressed_chunk_bytes, nvcompBatchedLZ4Opts_t format_opts, size_t* temp_bytes)
 {
-  if (temp_bytes == nullptr || !lz4_type_ok(format_opts.data_type)) {
-    return nvcompErrorInvalidValue;
-  }
-  if (max_uncompressed_chunk_bytes > nvcompLZ4CompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  /* the per-chunk hash tables live in LDS; the scratch is the persistent waves' ticket counter (common/lz_launch.hip.h) */
-  *temp_bytes = batch_size != 0 ? lzl::kTicketBytes : 0;
-  return nvcompSuccess;
+  const nvcompStatus_t st = temp_bytes == nullptr ? nvcompErrorInvalidValue : lz4_opts_status(format_opts, max_uncompressed_chunk_bytes);
+  return st != nvcompSuccess ? st : lzl::temp_size(batch_size, temp_bytes);
 }
 
 nvcompStatus_t nvcompBatchedLZ4CompressGetTempSizeEx(
@@ -575,14 +277,12 @@ nvcompStatus_t nvcompBatchedLZ4CompressGetTempSizeEx(
 nvcompStatus_t nvcompBatchedLZ4CompressGetMaxOutputChunkSize(
     size_t max_uncompressed_chunk_bytes, nvcompBatchedLZ4Opts_t format_opts, size_t* max_compressed_bytes)
 {
-  if (max_compressed_bytes == nullptr || !lz4_type_ok(format_opts.data_type)) {
-    return nvcompErrorInvalidValue;
+  const nvcompStatus_t st =
+      max_compressed_bytes == nullptr ? nvcompErrorInvalidValue : lz4_opts_status(format_opts, max_uncompressed_chunk_bytes);
+  if (st == nvcompSuccess) {
+    *max_compressed_bytes = lz4_bound(max_uncompressed_chunk_bytes);
   }
-  if (max_uncompressed_chunk_bytes > nvcompLZ4CompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  *max_compressed_bytes = lz4_bound(max_uncompressed_chunk_bytes);
-  return nvcompSuccess;
+  return st;
 }
 
 nvcompStatus_t nvcompBatchedLZ4CompressAsync(
@@ -597,75 +297,21 @@ nvcompStatus_t nvcompBatchedLZ4CompressAsync(
     nvcompBatchedLZ4Opts_t format_opts,
     hipStream_t stream)
 {
-  nvlog::call(3, "nvcompBatchedLZ4CompressAsync(batch_size=%zu, max_uncompressed_chunk_bytes=%zu, stream=%p)", batch_size,
-              max_uncompressed_chunk_bytes, (void*)stream);
-  if (!lz4_type_ok(format_opts.data_type)) {
-    return nvcompErrorInvalidValue;
-  }
-  if (max_uncompressed_chunk_bytes > nvcompLZ4CompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_uncompressed_ptrs == nullptr || device_uncompressed_bytes == nullptr || device_compressed_ptrs == nullptr
-      || device_compressed_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  /* persistent waves when the caller's temp buffer holds the ticket counter: as many workgroups as stay resident */
-#define NVCOMP_LZ4_COMPRESS(STRIDE)                                                                                       \
-  do {                                                                                                                    \
-    unsigned groups = (unsigned)((batch_size + kEncWaves - 1) / kEncWaves);                                               \
-    uint32_t* ticket = nullptr;                                                                                           \
-    if (NVCOMP_LZ_PERSISTENT && device_temp_ptr != nullptr && temp_bytes >= sizeof(uint32_t)                              \
-        && ((uintptr_t)device_temp_ptr & 3u) == 0) {                                                                      \
-      static lzl::ResidentCache resident; /* per device ordinal */                                                      \
-      const unsigned fit = resident.get(lz4_compress_kernel<STRIDE>, 64 * kEncWaves, 0);                                 \
-      if (fit != 0 && fit < groups && hipMemsetAsync(device_temp_ptr, 0, sizeof(uint32_t), stream) == hipSuccess) {       \
-        ticket = (uint32_t*)device_temp_ptr;                                                                              \
-        groups = fit;                                                                                                     \
-      }                                                                                                                   \
-    }                                                                                                                     \
-    const lzl::CompressLaunch launch = {device_uncompressed_ptrs, device_uncompressed_bytes, max_uncompressed_chunk_bytes, \
-                                        batch_size, device_compressed_ptrs, device_compressed_bytes, ticket,             \
-                                        (size_t)groups * kEncWaves};                                                      \
-    hipLaunchKernelGGL((lz4_compress_kernel<STRIDE>), dim3(groups), dim3(64 * kEncWaves), 0, stream, launch);             \
-  } while (0)
-#define NVCOMP_LZ4_COMPRESS_WIDE()                                                                                        \
-  do {                                                                                                                    \
-    unsigned groups = (unsigned)((batch_size + kWideWaves - 1) / kWideWaves);                                             \
-    uint32_t* ticket = nullptr;                                                                                           \
-    if (NVCOMP_LZ_PERSISTENT && device_temp_ptr != nullptr && temp_bytes >= sizeof(uint32_t)                              \
-        && ((uintptr_t)device_temp_ptr & 3u) == 0) {                                                                      \
-      static lzl::ResidentCache resident; /* per device ordinal */                                                      \
-      const unsigned fit = resident.get(lz4_compress_wide_kernel, 64 * kWideWaves, 0);                                   \
-      if (fit != 0 && fit < groups && hipMemsetAsync(device_temp_ptr, 0, sizeof(uint32_t), stream) == hipSuccess) {       \
-        ticket = (uint32_t*)device_temp_ptr;                                                                              \
-        groups = fit;                                                                                                     \
-      }                                                                                                                   \
-    }                                                                                                                     \
-    const lzl::CompressLaunch launch = {device_uncompressed_ptrs, device_uncompressed_bytes, max_uncompressed_chunk_bytes, \
-                                        batch_size, device_compressed_ptrs, device_compressed_bytes, ticket,             \
-                                        (size_t)groups * kWideWaves};                                                     \
-    hipLaunchKernelGGL(lz4_compress_wide_kernel, dim3(groups), dim3(64 * kWideWaves), 0, stream, launch);                 \
-  } while (0)
+  const lzl::CompressCall call = {"LZ4", lz4_opts_status(format_opts, max_uncompressed_chunk_bytes), device_uncompressed_ptrs,
+                                  device_uncompressed_bytes, max_uncompressed_chunk_bytes, batch_size, device_temp_ptr, temp_bytes,
+                                  device_compressed_ptrs, device_compressed_bytes, stream};
   switch (format_opts.data_type) {
   case NVCOMP_TYPE_SHORT:
-  case NVCOMP_TYPE_USHORT: NVCOMP_LZ4_COMPRESS(2); break;
+  case NVCOMP_TYPE_USHORT: return lzl::compress_async<lz4_compress_kernel<2>, kEncWaves>(call);
   case NVCOMP_TYPE_INT:
-  case NVCOMP_TYPE_UINT: NVCOMP_LZ4_COMPRESS(4); break;
+  case NVCOMP_TYPE_UINT: return lzl::compress_async<lz4_compress_kernel<4>, kEncWaves>(call);
   default:
 #if NVCOMP_LZM_WIDE
-    NVCOMP_LZ4_COMPRESS_WIDE();
+    return lzl::compress_async<lz4_compress_wide_kernel, kWideWaves>(call);
 #else
-    NVCOMP_LZ4_COMPRESS(1);
+    return lzl::compress_async<lz4_compress_kernel<1>, kEncWaves>(call);
 #endif
-    break;
   }
-#undef NVCOMP_LZ4_COMPRESS
-#undef NVCOMP_LZ4_COMPRESS_WIDE
-  return launch_status();
 }
 
 } // extern "C"
@@ -674,16 +320,7 @@ nvcompStatus_t nvcompBatchedLZ4CompressAsync(
 /* Profiling builds only: read (and clear) the per-phase cycle sums of the LZ4 compressor. */
 extern "C" int nvcompAmdCompProfRead(unsigned long long* host_slots, int n)
 {
-  unsigned long long v[lzm::kProfSlots] = {};
-  if (hipMemcpyFromSymbol(v, HIP_SYMBOL(lzm::g_prof), sizeof(v)) != hipSuccess) {
-    return -1;
-  }
-  for (int i = 0; i < n && i < (int)lzm::kProfSlots; ++i) {
-    host_slots[i] = v[i];
-  }
-  unsigned long long z[lzm::kProfSlots] = {};
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(lzm::g_prof), z, sizeof(z));
-  return (int)lzm::kProfSlots;
+  return prof_read_and_clear<lzm::kProfSlots>(lzm::g_prof, host_slots, n);
 }
 #endif
 
@@ -691,15 +328,6 @@ extern "C" int nvcompAmdCompProfRead(unsigned long long* host_slots, int n)
 /* Profiling builds only: read (and clear) the per-phase cycle sums of the window decoder. */
 extern "C" int nvcompAmdProfRead(unsigned long long* host_slots, int n)
 {
-  unsigned long long v[lzw::kProfSlots] = {};
-  if (hipMemcpyFromSymbol(v, HIP_SYMBOL(lzw::g_prof), sizeof(v)) != hipSuccess) {
-    return -1;
-  }
-  for (int i = 0; i < n && i < (int)lzw::kProfSlots; ++i) {
-    host_slots[i] = v[i];
-  }
-  unsigned long long z[lzw::kProfSlots] = {};
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(lzw::g_prof), z, sizeof(z));
-  return (int)lzw::kProfSlots;
+  return prof_read_and_clear<lzw::kProfSlots>(lzw::g_prof, host_slots, n);
 }
 #endif

@@ -9,6 +9,7 @@
 
 #include "nvcomp/zstd.h"
 
+#include "common/api_launch.h"
 #include "common/log.h"
 #include "common/lz_launch.hip.h"
 
@@ -86,18 +87,6 @@ __global__ void __launch_bounds__(256) zstd_size_kernel(
   }
   const size_t n = comp_bytes[chunk];
   uncompressed_bytes[chunk] = n > (1u << 28) ? 0 : zstd::content_size((const uint8_t*)comp_ptrs[chunk], (uint32_t)n);
-}
-
-/* hipGetLastError() is sticky per host thread: an unrelated earlier runtime call of the application must not be
- * reported as this launch's failure, so the slate is cleared before launching. */
-void clear_stale_error()
-{
-  (void)hipGetLastError();
-}
-
-nvcompStatus_t launch_status()
-{
-  return hipGetLastError() == hipSuccess ? nvcompSuccess : nvcompErrorCudaError;
 }
 
 size_t slot_for(size_t max_chunk)

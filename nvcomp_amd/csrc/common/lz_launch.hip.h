@@ -15,6 +15,9 @@
  * (producer / consumer, lz4_decode_window.hip.h: pair), which the team supersedes where both apply. The thresholds are
  * compile-time constants: the library has no run-time tuning state (tests force each path with an A/B build of this
  * file's macros).
+ *
+ * This file holds the thresholds, the kernels' parameter structs and the residency query. The launches themselves
+ * (persistent or static, the dispatch by batch size) and the kernel bodies LZ4 and Snappy share are common/lz_api.hip.h.
  */
 #pragma once
 

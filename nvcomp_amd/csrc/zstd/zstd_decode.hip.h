@@ -769,7 +769,7 @@ __device__ __forceinline__ uint32_t decode_chunk(
         return 0;
       }
       if (type == 0 || type == 1) {
-        const uint32_t need = type == 0 ? bsize : (bsize ? 1u : 0u);
+        const uint32_t need = type == 0 ? bsize : 1u; /* an RLE block carries its byte even when it repeats it 0 times */
         if (need > in_len - pos) {
           err |= lz::kErrInput;
           return 0;

@@ -48,7 +48,8 @@ static_assert(lzl::kIndexBytesPerWave >= lzx::kScratchPerWave, "a wave's slice o
 /* LZ4 as common/lz_api.hip.h sees it. */
 struct Lz4
 {
-  using TeamFrontEnd = lz4w::TeamFrontEnd;
+  using FrontEnd = lz4w::FrontEnd;
+  static constexpr bool kPairRuns = NVCOMP_LZ4_PAIR_RUNS != 0;
   static constexpr bool kEmptyIsError = false;
   /* a chunk that shrank 8 x or more (by the caller's capacity: an LZ4 block does not say what it decodes to) takes the
    * instance of the loop that tries the run executor; everything else the one without it (lz4w::decode_chunk) */
@@ -57,16 +58,6 @@ struct Lz4
   static __device__ __forceinline__ uint32_t alone(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint8_t* lds, uint32_t& err)
   {
     return lz4w::decode_chunk<CHECKED, 0, true>(in, n, out, cap, lds, err, nullptr);
-  }
-  template <bool CHECKED>
-  static __device__ __forceinline__ void produce(const uint8_t* in, uint32_t n, uint8_t* lds)
-  {
-    lz4w::pair::produce(in, n, lds);
-  }
-  template <bool CHECKED, bool TEAM>
-  static __device__ __forceinline__ uint32_t consume(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint8_t* lds, uint32_t& err)
-  {
-    return lz4w::pair::consume<CHECKED, !TEAM && NVCOMP_LZ4_PAIR_RUNS != 0>(in, n, out, cap, lds, err);
   }
 };
 

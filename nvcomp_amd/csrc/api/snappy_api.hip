@@ -34,7 +34,8 @@ constexpr size_t kRunsRatio = NVCOMP_SNAPPY_RUNS_RATIO;
 /* Snappy as common/lz_api.hip.h sees it. */
 struct Snappy
 {
-  using TeamFrontEnd = snappyw::TeamFrontEnd;
+  using FrontEnd = snappyw::FrontEnd;
+  static constexpr bool kPairRuns = false; /* the runs of a typed column go to alone() */
   static constexpr bool kEmptyIsError = true; /* an empty stream has no preamble: malformed */
   /* a chunk that shrank 8 x or more takes the instance of the loop that tries the run executor (snappyw::decode_chunk) */
   static __device__ __forceinline__ bool runs(size_t in_len, size_t cap)
@@ -45,16 +46,6 @@ struct Snappy
   static __device__ __forceinline__ uint32_t alone(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint8_t* lds, uint32_t& err)
   {
     return snappyw::decode_chunk<CHECKED, true>(in, n, out, cap, lds, err);
-  }
-  template <bool CHECKED>
-  static __device__ __forceinline__ void produce(const uint8_t* in, uint32_t n, uint8_t* lds)
-  {
-    snappyw::pair::produce<CHECKED>(in, n, lds);
-  }
-  template <bool CHECKED, bool TEAM>
-  static __device__ __forceinline__ uint32_t consume(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint8_t* lds, uint32_t& err)
-  {
-    return snappyw::pair::consume<CHECKED>(in, n, out, cap, lds, err);
   }
 };
 

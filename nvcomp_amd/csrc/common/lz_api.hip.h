@@ -5,12 +5,11 @@
  *
  * The __global__ functions stay in the two files, under their own names and with their __shared__ arrays; each declares
  * its LDS and calls a body here. A FORMAT is a struct of static functions (Lz4, Snappy in the two files):
- *   using TeamFrontEnd                  the front end of common/lz_team.hip.h
+ *   using FrontEnd                      what the team (common/lz_team.hip.h) and the two waves (common/lz_pair.hip.h) decode with
  *   kEmptyIsError                       whether a stream of 0 bytes is malformed (Snappy: no preamble) or decodes to nothing (LZ4)
  *   runs(in_len, cap)                   whether the chunk shrank enough to try the run executor
  *   alone<CHECKED>(in, n, out, cap, lds, err)           the one-wave loop that holds the run executor
- *   produce<CHECKED>(in, n, lds)                        the two-wave kernel's first wave
- *   consume<CHECKED, TEAM>(in, n, out, cap, lds, err)   ... and its second (TEAM: as a team's fallback)
+ *   kPairRuns                           whether the two-wave kernel's consumer tries the run executor (not as a team's fallback)
  */
 #pragma once
 
@@ -21,6 +20,7 @@
 #include "common/log.h"
 #include "common/lz_launch.hip.h"
 #include "common/lz_window.hip.h"
+#include "common/lz_pair.hip.h"
 #include "common/lz_team.hip.h"
 
 #ifndef NVCOMP_LZ_DEC_WAVES_PER_BLOCK
@@ -122,7 +122,7 @@ __device__ __forceinline__ void decode_window_loop(const Launch& launch, uint32_
 #endif
 }
 
-/* Small batches: two waves per chunk, a producer (chase + parse) and a consumer (execute), lzw::pair. `lds`: the workgroup's
+/* Small batches: two waves per chunk, a producer (chase + parse) and a consumer (execute), common/lz_pair.hip.h. `lds`: the workgroup's
  * lzw::pair::kLdsPerChunk bytes. */
 template <bool CHECKED, class Format>
 __device__ __forceinline__ void decode_pair(const Batch& b, uint8_t* lds)
@@ -132,9 +132,7 @@ __device__ __forceinline__ void decode_pair(const Batch& b, uint8_t* lds)
   if (chunk >= b.batch_size) {
     return;
   }
-  if (threadIdx.x < 4) {
-    ((uint32_t*)(lds + lzw::pair::kLdsPerChunk - lzw::pair::kCtrlBytes))[threadIdx.x] = 0; /* both slots empty, no abort */
-  }
+  lzw::pair::reset_control(lds);
   __syncthreads();
   const Chunk c = fetch_chunk(&b, chunk);
   const bool work = !c.too_long() && c.in_len != 0;
@@ -146,7 +144,7 @@ __device__ __forceinline__ void decode_pair(const Batch& b, uint8_t* lds)
   const bool solo = NVCOMP_LZ_PAIR_SOLO && work && Format::runs(c.in_len, c.cap);
   if (w == 0) {
     if (work && !solo) {
-      Format::template produce<CHECKED>(c.in, (uint32_t)c.in_len, lds);
+      lzw::pair::produce<typename Format::FrontEnd, CHECKED>(c.in, (uint32_t)c.in_len, lds);
     }
     return;
   }
@@ -155,7 +153,7 @@ __device__ __forceinline__ void decode_pair(const Batch& b, uint8_t* lds)
   if (solo) {
     produced = Format::template alone<CHECKED>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds, err);
   } else if (work) {
-    produced = Format::template consume<CHECKED, false>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds, err);
+    produced = lzw::pair::consume<typename Format::FrontEnd, CHECKED, Format::kPairRuns>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds, err);
   }
   if (wave::lane_id() == 0) {
     report<CHECKED>(&b, chunk, produced, err);
@@ -183,7 +181,7 @@ __device__ __forceinline__ void decode_team_loop(const Launch& launch, uint8_t* 
     if (c.too_long()) {
       err = lz::kErrInput;
     } else {
-      produced = lzt::decode_chunk<typename Format::TeamFrontEnd, WAVES>(
+      produced = lzt::decode_chunk<typename Format::FrontEnd, WAVES>(
           c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds, err,
           [](uint32_t role, const uint8_t* i, uint32_t n, uint8_t* o, uint32_t cap, uint8_t* scratch, uint32_t& e) -> uint32_t {
             /* the team's fallback is the two-wave kernel: chunks that shrank 8 x (here: mostly the 16 x ones of the team's
@@ -191,14 +189,14 @@ __device__ __forceinline__ void decode_team_loop(const Launch& launch, uint8_t* 
             const bool solo = NVCOMP_LZ_PAIR_SOLO && Format::runs(n, cap);
             if (role == 0) {
               if (!solo) {
-                Format::template produce<true>(i, n, scratch);
+                lzw::pair::produce<typename Format::FrontEnd, true>(i, n, scratch);
               }
               return 0u;
             }
             if (solo) {
               return Format::template alone<true>(i, n, o, cap, scratch, e);
             }
-            return Format::template consume<true, true>(i, n, o, cap, scratch, e);
+            return lzw::pair::consume<typename Format::FrontEnd, true, false>(i, n, o, cap, scratch, e);
           });
     }
     a = wave::kernel_args(launch);

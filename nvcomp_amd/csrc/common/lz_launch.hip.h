@@ -12,7 +12,7 @@
  *
  * PATH BY BATCH SIZE. Batches of at most kTeamMaxBatch chunks cannot fill the card with one wave per chunk and run a
  * WORKGROUP of eight waves per chunk (common/lz_team.hip.h); kPairMaxBatch is the same for round 2's two waves per chunk
- * (producer / consumer, lz4_decode_window.hip.h: pair), which the team supersedes where both apply. The thresholds are
+ * (producer / consumer, common/lz_pair.hip.h), which the team supersedes where both apply. The thresholds are
  * compile-time constants: the library has no run-time tuning state (tests force each path with an A/B build of this
  * file's macros).
  *

@@ -37,6 +37,7 @@
 #endif
 
 #include "common/lz_window.hip.h"
+#include "common/lz_pair.hip.h"
 
 namespace lzt {
 
@@ -265,15 +266,13 @@ __device__ __forceinline__ uint32_t cnt_read4(const uint32_t* cnt, uint32_t g)
 }
 
 /* A chunk that is not a team's (more than 64 KiB of capacity or stream, or a stream that breaks the in-place invariant):
- * waves 0 and 1 decode it as producer and consumer (lz4_decode_window.hip.h: pair) in the table area, the others wait.
+ * waves 0 and 1 decode it as producer and consumer (common/lz_pair.hip.h) in the table area, the others wait.
  * `fallback(role, ...)`: role 0 produces, role 1 consumes and returns the bytes produced. */
 template <class Fallback>
 __device__ __forceinline__ uint32_t run_fallback(
     const Team& t, uint8_t* scratch, const uint8_t* in, uint32_t in_len, uint8_t* out, uint32_t out_cap, uint32_t& err, Fallback fallback)
 {
-  if (threadIdx.x < 4) {
-    ((uint32_t*)(scratch + lzw::pair::kLdsPerChunk - lzw::pair::kCtrlBytes))[threadIdx.x] = 0; /* both slots empty, no abort */
-  }
+  lzw::pair::reset_control(scratch);
   __syncthreads();
   if (t.w < 2) {
     uint32_t e = lz::kErrNone;

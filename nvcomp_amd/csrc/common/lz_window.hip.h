@@ -231,10 +231,25 @@ __device__ __forceinline__ uint32_t in_byte_uniform(const R& r, uint32_t v)
   return wave::uniform(in_byte(r, v));
 }
 
+/* The 8 stream bytes at virtual position p -- those of them that are resident, the others are whatever the ring
+ * holds there: three aligned dword reads (a misaligned ds_read_b32 is served lane by lane) and a funnel shift. */
+template <class R>
+__device__ __forceinline__ uint64_t ring_bytes8(const R& r, uint32_t p)
+{
+  const uint32_t m = R::kMask;
+  const uint32_t a0 = p & ~3u;
+  const uint32_t d0 = *(const uint32_t*)(r.ring + (a0 & m));
+  const uint32_t d1 = *(const uint32_t*)(r.ring + ((a0 + 4) & m));
+  const uint32_t d2 = *(const uint32_t*)(r.ring + ((a0 + 8) & m));
+  const uint32_t lo = wave::align_bytes(d1, d0, p & 3u);
+  const uint32_t hi = wave::align_bytes(d2, d1, p & 3u);
+  return ((uint64_t)hi << 32) | lo;
+}
+
 /* ---- token chase by pointer doubling ------------------------------------------
  *
  * The format-specific part is a functor `delta(r, p)`: the distance from a (speculative)
- * token at virtual position p to the token after it, or kUnknownDelta when that cannot be
+ * token at virtual position p to the token after it, or kUnknown when that cannot be
  * told from the resident bytes. For a window of 256 positions the wave builds, in LDS,
  * byte tables J_i[p] = distance from p to the 2^i-th token after p (255 = leaves the
  * window / unknown), i = 0..5, by five doubling rounds J_i[p] = J_{i-1}[p] + J_{i-1}[p +
@@ -243,7 +258,9 @@ __device__ __forceinline__ uint32_t in_byte_uniform(const R& r, uint32_t v)
  * 64 dependent scalar steps. The tables do not depend on the start, so a window is built
  * once however many batches it feeds. */
 
-constexpr uint32_t kUnknownDelta = 1u << 28; /* chunk sizes are < 2^28 */
+/* Delta stored for a position whose next token cannot be derived in the parallel
+ * pass (chunk sizes are < 2^28, so position + kUnknown never looks like a position). */
+constexpr uint32_t kUnknown = 1u << 28;
 constexpr uint32_t kNxUnknown = 0xffffu;     /* the same in the 16-bit form the chase keeps (real deltas are < 2^15) */
 
 struct Chase
@@ -295,10 +312,10 @@ __device__ __forceinline__ void chase_build(Chase& c, const R& r, Delta delta, u
     }
     /* what the straight-line form gave up on gets the general one (a branch for the wave: rare on text, every window
      * of a sorted column, whose matches take a second length byte) */
-    if (Delta::kSecondChance && wave::ballot((nx[0] | nx[1] | nx[2] | nx[3]) >= kUnknownDelta)) {
+    if (Delta::kSecondChance && wave::ballot((nx[0] | nx[1] | nx[2] | nx[3]) >= kUnknown)) {
 #pragma unroll
       for (uint32_t k = 0; k < 4; ++k) {
-        if (nx[k] >= kUnknownDelta) {
+        if (nx[k] >= kUnknown) {
           nx[k] = delta.second(r, base + k, w >> (8 * k));
         }
       }
@@ -337,7 +354,7 @@ __device__ __forceinline__ void chase_build(Chase& c, const R& r, Delta delta, u
 }
 
 /* Append token positions to seqpos lanes [k, 64); returns the new count. `slow(r, p)`
- * gives the successor of the token at p when its delta is kUnknownDelta.
+ * gives the successor of the token at p when its delta is kUnknown.
  * (A window's ~54 tokens and a batch's 64 never line up: every batch enumerates 2.2 times. Round 6 kept what an
  * enumeration found and the batch had no room for in a register and handed it to the next batch with a shuffle -- 36 vector
  * instructions fewer per batch, and slower: mix 648 -> 646 GB/s, Snappy 481 -> 473, text 596 -> 558 (gpurun r6n); one more
@@ -557,42 +574,6 @@ __device__ __forceinline__ void drop_front(lz::Seq& s, uint32_t take, uint32_t c
   s.match_off = keep ? c : 0u;
   s.match_len = keep ? d : 0u;
 }
-
-/* ---- two waves per chunk: what the producer and the consumer share (lz4_decode_window.hip.h: pair) ---- */
-namespace pair {
-
-constexpr uint32_t kSlotBytes = 16 + 4 * 64 * 4; /* n, flags, pad | lit_src[64] | lit_len[64] | match_off[64] | match_len[64] */
-constexpr uint32_t kFlagLast = 1, kFlagBad = 2;
-constexpr uint32_t kCtrlBytes = 16; /* state[2], abort, pad */
-/* window | consumer ring | producer ring | chase tables | two slots | control */
-constexpr uint32_t kLdsPerChunk = lzw::kOutLds + 2 * lzw::kInLds + lzw::kChaseLds + 2 * kSlotBytes + kCtrlBytes;
-
-struct Shared
-{
-  uint8_t* slots;  /* two of kSlotBytes each: slot(k) -- not an array of two pointers: indexed by a run-time k, that array
-                    * lived in scratch memory (40 bytes per lane, a scratch load per hand-over) */
-  uint32_t* state; /* [2]: 0 = empty, 1 = full */
-  uint32_t* abort; /* the consumer gave up: the producer stops waiting */
-  __device__ __forceinline__ uint8_t* slot(uint32_t k) const { return slots + k * kSlotBytes; }
-};
-
-__device__ __forceinline__ Shared shared_at(uint8_t* lds)
-{
-  uint8_t* q = lds + lzw::kOutLds + 2 * lzw::kInLds + lzw::kChaseLds;
-  Shared sh;
-  sh.slots = q;
-  sh.state = (uint32_t*)(q + 2 * kSlotBytes);
-  sh.abort = sh.state + 2;
-  return sh;
-}
-
-/* lane 0's view of a flag word, the same for the whole wave */
-__device__ __forceinline__ uint32_t poll(const uint32_t* p)
-{
-  return wave::read_lane(wave::lds_load_acquire(p), 0);
-}
-
-} // namespace pair
 
 /* ---- LDS copies ------------------------------------------------------------ */
 

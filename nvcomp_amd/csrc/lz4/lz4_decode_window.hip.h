@@ -17,34 +17,8 @@
 
 namespace lz4w {
 
-/* Delta stored for a position whose next token cannot be derived in the parallel
- * pass (chunk sizes are < 2^28, so position + kUnknown never looks like a position). */
-constexpr uint32_t kUnknown = 1u << 28;
-
-
-/* The 8 (4) stream bytes at virtual position p -- those of them that are resident, the others are whatever the ring
- * holds there: three (two) aligned dword reads (a misaligned ds_read_b32 is served lane by lane) and a funnel shift. */
-template <class R>
-__device__ __forceinline__ uint64_t ring_bytes8(const R& r, uint32_t p)
-{
-  const uint32_t m = R::kMask;
-  const uint32_t a0 = p & ~3u;
-  const uint32_t d0 = *(const uint32_t*)(r.ring + (a0 & m));
-  const uint32_t d1 = *(const uint32_t*)(r.ring + ((a0 + 4) & m));
-  const uint32_t d2 = *(const uint32_t*)(r.ring + ((a0 + 8) & m));
-  const uint32_t lo = wave::align_bytes(d1, d0, p & 3u);
-  const uint32_t hi = wave::align_bytes(d2, d1, p & 3u);
-  return ((uint64_t)hi << 32) | lo;
-}
-template <class R>
-__device__ __forceinline__ uint32_t ring_bytes4(const R& r, uint32_t p)
-{
-  const uint32_t m = R::kMask;
-  const uint32_t a0 = p & ~3u;
-  const uint32_t d0 = *(const uint32_t*)(r.ring + (a0 & m));
-  const uint32_t d1 = *(const uint32_t*)(r.ring + ((a0 + 4) & m));
-  return wave::align_bytes(d1, d0, p & 3u);
-}
+using lzw::kUnknown;
+using lzw::ring_bytes8;
 
 /* A length field behind a nibble of 15, its bytes in `f` from bit 0 on (six of them, zeros above): how many of them are
  * 255 (0 .. 6; 6 = the field goes on behind what f holds) */
@@ -360,8 +334,9 @@ struct IndexFormat
   }
 };
 
-/* What the workgroup-per-chunk decoder (common/lz_team.hip.h) needs to know of the format. */
-struct TeamFrontEnd
+/* What the workgroup-per-chunk decoder (common/lz_team.hip.h) and the two-wave decoder (common/lz_pair.hip.h) need to know
+ * of the format. */
+struct FrontEnd
 {
   static constexpr uint32_t kPositions = 192; /* a sequence is at least 3 bytes (token + offset): 64 tokens at most */
   static constexpr bool kEmptyIsError = false; /* an empty block decodes to nothing */
@@ -369,6 +344,7 @@ struct TeamFrontEnd
   using Delta = DeltaFn;
   using Slow = SlowFn;
   /* an LZ4 block does not say what it decodes to: the caller's capacity decides (pass tight capacities for the team path) */
+  static constexpr bool kDeclaresLength = false;
   static __device__ __forceinline__ uint32_t declared_length(const uint8_t*, uint32_t) { return ~0u; }
   template <class R>
   static __device__ __forceinline__ bool begin(const R& r, uint32_t out_cap, uint32_t& q, uint32_t& limit, uint32_t&)
@@ -383,6 +359,21 @@ struct TeamFrontEnd
   {
     lz4w::parse_batch(r, p, from, to, s, bad);
   }
+  /* the two waves: the tokens start with the block */
+  static __device__ __forceinline__ bool open(lzw::InRing& ir, uint32_t& q, uint32_t& total)
+  {
+    q = ir.vbeg;
+    total = 0;
+    return true;
+  }
+  /* every sequence has a position, in stream order: from the first one's literals to the last one's */
+  static __device__ __forceinline__ void ensure_literals(lzw::InRing& ir, const lz::Seq& s, uint32_t count)
+  {
+    const uint32_t oldest = wave::read_lane(s.lit_src, 0);
+    const uint32_t newest = wave::read_lane(s.lit_src, count - 1);
+    lzw::in_ensure(ir, oldest, (newest & ~(lzw::kInBlock - 1)) + 2 * lzw::kInBlock);
+  }
+  static __device__ __forceinline__ uint32_t streamed_take(const lz::Seq&, uint32_t) { return 1; }
 };
 
 /* Decode one chunk with the calling wave; `lds` is this wave's kLdsPerWave bytes. */
@@ -525,160 +516,5 @@ __device__ __forceinline__ uint32_t decode_chunk(
   lzw::out_flush_all(ow, op);
   return op;
 }
-
-/* ---- two waves per chunk (small batches) -----------------------------------------------------------------------
- *
- * One wave per chunk leaves the card under-filled below ~7 000 chunks, and a 64 KiB chunk takes a wave ~0.75 ms
- * however idle the CU is: the wave's own dependent chain -- chase, parse, far loads, copy rounds, flush -- is what
- * takes the time (profiles/archive/r02_decode_phases.json). For small batches the chain is cut in two: wave 0 of a 128-thread
- * workgroup (the PRODUCER) runs the token chase and the parse and hands batches of parsed sequences to wave 1 (the
- * CONSUMER), which executes them; the two overlap, a chunk takes about as long as its slower half. Hand-over is a
- * two-slot queue in LDS with one flag word per slot (wave::lds_store_release / lds_load_acquire). The producer never
- * depends on anything the consumer does except a free slot; each wave keeps its own ring over the compressed stream
- * (the consumer's serves the literal copies), so nothing else is shared. Same bytes as decode_chunk.
- */
-namespace pair {
-
-using namespace lzw::pair;
-
-__device__ __forceinline__ void produce(const uint8_t* __restrict__ in, uint32_t in_len, uint8_t* lds)
-{
-  const uint32_t lane = (uint32_t)wave::lane_id();
-  const Shared sh = shared_at(lds);
-  lzw::InRing ir;
-  lzw::in_init(ir, in, in_len, lds + lzw::kOutLds + lzw::kInLds);
-  lzw::Chase c;
-  lzw::chase_init(c, ir.vbeg, lds + lzw::kOutLds + 2 * lzw::kInLds);
-  uint32_t k = 0;
-  for (;;) {
-    const bool last = c.q >= ir.vend;
-    uint32_t count = 0;
-    lz::Seq s;
-    s.lit_src = 0, s.lit_len = 0, s.match_off = 0, s.match_len = 0;
-    bool bad = false;
-    if (!last) {
-      lzw::in_ensure(ir, c.q, (c.q & ~(lzw::kInBlock - 1)) + 3 * lzw::kInBlock);
-      uint32_t seqpos = 0;
-      count = lzw::chase_tokens(c, ir, seqpos, 0, DeltaFn(), SlowFn());
-      parse_batch(ir, seqpos, 0, count, s, bad);
-    }
-    const uint32_t flags = (last ? kFlagLast : 0u) | (wave::ballot(bad) ? kFlagBad : 0u);
-    while (poll(sh.state + k) != 0) {
-      if (poll(sh.abort) != 0) {
-        return;
-      }
-      wave::nap();
-    }
-    uint32_t* f = (uint32_t*)(sh.slot(k) + 16);
-    f[lane] = s.lit_src;
-    f[64 + lane] = s.lit_len;
-    f[128 + lane] = s.match_off;
-    f[192 + lane] = s.match_len;
-    if (lane == 0) {
-      ((uint32_t*)sh.slot(k))[0] = count;
-      ((uint32_t*)sh.slot(k))[1] = flags;
-    }
-    wave::sync();
-    if (lane == 0) {
-      wave::lds_store_release(sh.state + k, 1u);
-    }
-    if (flags) {
-      return; /* the end of the chunk, or a malformed token: nothing follows */
-    }
-    k ^= 1;
-  }
-}
-
-template <bool CHECKED, bool RUNS = false>
-__device__ __forceinline__ uint32_t consume(
-    const uint8_t* __restrict__ in, uint32_t in_len, uint8_t* out, uint32_t out_cap, uint8_t* lds, uint32_t& err)
-{
-  const uint32_t lane = (uint32_t)wave::lane_id();
-  const Shared sh = shared_at(lds);
-  lzw::InRing ir;
-  lzw::OutWindow ow;
-  lzw::in_init(ir, in, in_len, lds + lzw::kOutLds);
-  lzw::out_init(ow, out, lds);
-  uint32_t op = 0;
-  uint32_t count = 0;
-  uint32_t k = 0;
-  lzw::RunGate gate = lzw::kRunGateInit;
-  lz::Seq s;
-  s.lit_src = 0, s.lit_len = 0, s.match_off = 0, s.match_len = 0;
-  for (;;) {
-    if (count == 0) {
-      while (poll(sh.state + k) != 1) {
-        wave::nap();
-      }
-      const uint32_t* f = (const uint32_t*)(sh.slot(k) + 16);
-      s.lit_src = f[lane];
-      s.lit_len = f[64 + lane];
-      s.match_off = f[128 + lane];
-      s.match_len = f[192 + lane];
-      const uint32_t n = wave::read_lane(((const uint32_t*)sh.slot(k))[0], 0);
-      const uint32_t flags = wave::read_lane(((const uint32_t*)sh.slot(k))[1], 0);
-      wave::sync();
-      if (lane == 0) {
-        wave::lds_store_release(sh.state + k, 0u);
-      }
-      k ^= 1;
-      if (flags & kFlagBad) {
-        err |= lz::kErrInput;
-        return 0;
-      }
-      if (flags & kFlagLast) {
-        break;
-      }
-      count = n;
-      if (count == 0) {
-        continue;
-      }
-    }
-    /* the literal copies read this wave's own ring */
-    {
-      const uint32_t oldest = wave::read_lane(s.lit_src, 0);
-      const uint32_t newest = wave::read_lane(s.lit_src, count - 1);
-      lzw::in_ensure(ir, oldest, (newest & ~(lzw::kInBlock - 1)) + 2 * lzw::kInBlock);
-    }
-    bool big = false;
-    uint32_t take = 0;
-    if (RUNS && lzw::run_gate_open(gate)) {
-      bool misfit;
-      take = lzw::execute_run_batch<CHECKED>(ir, ow, out_cap, op, count, s, misfit);
-      gate = wave::uniform(lzw::run_gate_tried(gate, take, misfit));
-    }
-    if (take == 0) {
-      take = lzw::execute_window_batch<CHECKED>(ir, ow, out_cap, op, count, s, err, big);
-      if (RUNS) {
-        gate = wave::uniform(lzw::run_gate_window_took(gate, take, count));
-      }
-    }
-    if (CHECKED && err) {
-      if (lane == 0) {
-        wave::lds_store_release(sh.abort, 1u);
-      }
-      return 0;
-    }
-    if (big) {
-      /* the first sequence in hand has a long literal run or a long match, or is larger than a batch: straight to HBM */
-      if (!lzw::stream_sequence<CHECKED>(ir, ow, out_cap, op, wave::read_lane(s.lit_src, 0), wave::read_lane(s.lit_len, 0),
-                                         wave::read_lane(s.match_off, 0), wave::read_lane(s.match_len, 0), err)) {
-        if (lane == 0) {
-          wave::lds_store_release(sh.abort, 1u);
-        }
-        return 0;
-      }
-      take = 1;
-    }
-    if (take < count) {
-      lzw::drop_front(s, take, count);
-    }
-    count -= take;
-  }
-  lzw::out_flush_all(ow, op);
-  return op;
-}
-
-} // namespace pair
 
 } // namespace lz4w

@@ -181,19 +181,27 @@ __device__ __forceinline__ void parse(
   }
 }
 
+/* The varint32 preamble (uncompressed length) straight from memory, by every lane alike. False: malformed -- the stream
+ * ends inside it, or it does not fit 32 bits (a fifth byte above 15, or with its continuation bit set). Accepts exactly
+ * what read_preamble() above and snappyw::read_preamble() (through the stream ring) accept. */
+__device__ __forceinline__ bool preamble(const uint8_t* __restrict__ in, uint32_t in_len, uint32_t& total)
+{
+  total = 0;
+  for (uint32_t i = 0; i < 5 && i < in_len; ++i) {
+    const uint32_t b = in[i];
+    total |= (b & 127u) << (7 * i);
+    if (!(b & 128u)) {
+      return !(i == 4 && b > 15u);
+    }
+  }
+  return false;
+}
+
 /* Uncompressed length from the preamble; 0 if malformed. */
 __device__ __forceinline__ uint32_t decoded_size(const uint8_t* __restrict__ in, uint32_t in_len, bool& ok)
 {
-  Chase c;
-  lz::window_init(c.w, in, in_len);
-  c.q = c.w.vbeg;
-  uint32_t total = 0;
-  ok = false;
-  if (in_len == 0) {
-    return 0;
-  }
-  chase_reload(c, c.q);
-  ok = read_preamble(c, total);
+  uint32_t total;
+  ok = preamble(in, in_len, total);
   return ok ? total : 0;
 }
 

@@ -9,12 +9,12 @@
 #pragma once
 
 #include "common/lz_window.hip.h"
+#include "snappy/snappy_decode.hip.h"
 
 namespace snappyw {
 
-/* Delta stored for a position whose next token cannot be derived in the parallel
- * pass (chunk sizes are < 2^28, so position + kUnknown never looks like a position). */
-constexpr uint32_t kUnknown = 1u << 28;
+using lzw::kUnknown;
+using lzw::ring_bytes8;
 
 /* A token of the chase is one copy element, or a literal element together with the copy element that
  * follows it (when the literal element is at most kFuseMax bytes long and a copy does follow): the
@@ -200,21 +200,6 @@ __device__ __forceinline__ void parse(const R& r, uint32_t p, bool active, lz::S
   }
 }
 
-/* The 8 stream bytes at virtual position p (resident, p + 11 below the end of residency): aligned dword reads and a
- * funnel shift (a misaligned ds_read_b32 is served lane by lane). */
-template <class R>
-__device__ __forceinline__ uint64_t ring_bytes8(const R& r, uint32_t p)
-{
-  const uint32_t m = R::kMask;
-  const uint32_t a0 = p & ~3u;
-  const uint32_t d0 = *(const uint32_t*)(r.ring + (a0 & m));
-  const uint32_t d1 = *(const uint32_t*)(r.ring + ((a0 + 4) & m));
-  const uint32_t d2 = *(const uint32_t*)(r.ring + ((a0 + 8) & m));
-  const uint32_t lo = wave::align_bytes(d1, d0, p & 3u);
-  const uint32_t hi = wave::align_bytes(d2, d1, p & 3u);
-  return ((uint64_t)hi << 32) | lo;
-}
-
 /* parse() for the common batch, lanes [from, to) (to > from): literal elements of at most 60 bytes (no length bytes).
  * As in lz4_decode_window.hip.h, residency and the chunk's end are checked once for the wave from the first and the last
  * token position: a token of the fast kind spans at most kFastSpan stream bytes (tag, 60 literals, the fused copy's tag
@@ -306,28 +291,23 @@ __device__ __forceinline__ uint64_t merge_trains(lz::Seq& s, uint32_t count)
   return train;
 }
 
-/* What the workgroup-per-chunk decoder (common/lz_team.hip.h) needs to know of the format. */
-struct TeamFrontEnd
+/* What the workgroup-per-chunk decoder (common/lz_team.hip.h) and the two-wave decoder (common/lz_pair.hip.h) need to know
+ * of the format. */
+struct FrontEnd
 {
   static constexpr uint32_t kPositions = 128; /* a token is at least 2 bytes (a copy element with a one-byte offset) */
   static constexpr bool kEmptyIsError = true; /* no preamble */
   static constexpr uint32_t kFewLongMatchesRatio = 12; /* common/lz_team.hip.h: such chunks go to the two-wave decoder */
   using Delta = DeltaFn;
   using Slow = SlowFn;
+  static constexpr bool kDeclaresLength = true;
   /* What the stream says it decodes to (its varint32 preamble), read straight from memory by every lane alike; ~0u when
    * there is no complete preamble. The team decoder keeps a chunk on chip when THIS fits its buffer, whatever capacity the
    * caller passed (a rounded-up max_uncompressed_chunk_bytes, say: ADVICE r4). */
   static __device__ __forceinline__ uint32_t declared_length(const uint8_t* in, uint32_t in_len)
   {
-    uint32_t v = 0;
-    for (uint32_t i = 0; i < 5 && i < in_len; ++i) {
-      const uint32_t b = in[i];
-      v |= (b & 127u) << (7 * i);
-      if (!(b & 128u)) {
-        return (i == 4 && b > 15u) ? ~0u : v;
-      }
-    }
-    return ~0u;
+    uint32_t v;
+    return snappy::preamble(in, in_len, v) ? v : ~0u;
   }
   /* the preamble: first element, and the length the elements must produce exactly */
   template <class R>
@@ -357,6 +337,31 @@ struct TeamFrontEnd
   static __device__ __forceinline__ bool finish_ok(uint32_t op, uint32_t q, uint32_t vend, uint32_t limit)
   {
     return op == limit && q == vend;
+  }
+  /* the two waves: the preamble again, through the wave's own ring (its first block made resident) */
+  static __device__ __forceinline__ bool open(lzw::InRing& ir, uint32_t& q, uint32_t& total)
+  {
+    lzw::in_ensure(ir, ir.vbeg, ir.vbeg + lzw::kInBlock);
+    return read_preamble(ir, q, total);
+  }
+  /* copy elements carry no stream position: from the lowest to the highest of those that have literals */
+  static __device__ __forceinline__ void ensure_literals(lzw::InRing& ir, const lz::Seq& s, uint32_t count)
+  {
+    const uint32_t lane = (uint32_t)wave::lane_id();
+    const bool has_lit = lane < count && s.lit_len != 0;
+    if (wave::ballot(has_lit)) {
+      const uint32_t hi = wave::reduce_max(has_lit ? s.lit_src : 0u);
+      const uint32_t lo = ~wave::reduce_max(has_lit ? ~s.lit_src : 0u);
+      lzw::in_ensure(ir, lo, (hi & ~(lzw::kInBlock - 1)) + 2 * lzw::kInBlock);
+    }
+  }
+  /* sequence 0 and the empty sequences (the followers of its copy train) right behind it */
+  static __device__ __forceinline__ uint32_t streamed_take(const lz::Seq& s, uint32_t count)
+  {
+    const uint32_t lane = (uint32_t)wave::lane_id();
+    const uint64_t empty = wave::ballot(lane < count && s.lit_len + s.match_len == 0);
+    const uint32_t take = 1 + wave::ctz64(~(empty >> 1));
+    return take < count ? take : count;
   }
 };
 
@@ -484,7 +489,7 @@ __device__ __forceinline__ uint32_t decode_chunk(
     LZ_STAT("sn_rounds", 1);
     LZ_STAT("sn_rounds_with_train", train ? 1 : 0);
     bool big = false;
-    /* runs (typed columns: a literal element, then copies of period 1 .. 16) straight to the output: lzw::execute_run_batch */
+    /* runs (sorted keys, typed columns) are executed 60 at a time, straight to the output: lzw::execute_run_batch */
     static_assert(!NVCOMP_LZW_RUNS || lzw::kRunFits, "the run executor needs 2 176 bytes of window LDS");
     uint32_t take = 0;
     if (RUNS && lzw::run_gate_open(gate)) {
@@ -523,178 +528,5 @@ __device__ __forceinline__ uint32_t decode_chunk(
   lzw::out_flush_all(ow, op);
   return op;
 }
-
-/* ---- two waves per chunk (small batches): lz4_decode_window.hip.h has the description ---- */
-namespace pair {
-
-using namespace lzw::pair;
-
-template <bool CHECKED>
-__device__ __forceinline__ void produce(const uint8_t* __restrict__ in, uint32_t in_len, uint8_t* lds)
-{
-  const uint32_t lane = (uint32_t)wave::lane_id();
-  const Shared sh = shared_at(lds);
-  lzw::InRing ir;
-  lzw::in_init(ir, in, in_len, lds + lzw::kOutLds + lzw::kInLds);
-  lzw::in_ensure(ir, ir.vbeg, ir.vbeg + lzw::kInBlock);
-  uint32_t q, total;
-  const bool preamble_ok = read_preamble(ir, q, total);
-  lzw::Chase c;
-  lzw::chase_init(c, q, lds + lzw::kOutLds + 2 * lzw::kInLds);
-  uint32_t k = 0;
-  for (;;) {
-    const bool last = !preamble_ok || c.q >= ir.vend;
-    uint32_t count = 0;
-    lz::Seq s;
-    s.lit_src = 0, s.lit_len = 0, s.match_off = 0, s.match_len = 0;
-    bool bad = !preamble_ok || (last && CHECKED && c.q != ir.vend); /* the elements must end exactly at the end */
-    if (!last) {
-      lzw::in_ensure(ir, c.q, (c.q & ~(lzw::kInBlock - 1)) + 3 * lzw::kInBlock);
-      uint32_t seqpos = 0;
-      count = lzw::chase_tokens(c, ir, seqpos, 0, DeltaFn(), SlowFn());
-      if (count == 0 || !parse_fast(ir, seqpos, 0, count, s, bad)) {
-        parse(ir, seqpos, lane < count, s, bad);
-      }
-      (void)merge_trains(s, count);
-    }
-    const uint32_t flags = (last ? kFlagLast : 0u) | (wave::ballot(bad) ? kFlagBad : 0u);
-    while (poll(sh.state + k) != 0) {
-      if (poll(sh.abort) != 0) {
-        return;
-      }
-      wave::nap();
-    }
-    uint32_t* f = (uint32_t*)(sh.slot(k) + 16);
-    f[lane] = s.lit_src;
-    f[64 + lane] = s.lit_len;
-    f[128 + lane] = s.match_off;
-    f[192 + lane] = s.match_len;
-    if (lane == 0) {
-      ((uint32_t*)sh.slot(k))[0] = count;
-      ((uint32_t*)sh.slot(k))[1] = flags;
-    }
-    wave::sync();
-    if (lane == 0) {
-      wave::lds_store_release(sh.state + k, 1u);
-    }
-    if (flags) {
-      return;
-    }
-    k ^= 1;
-  }
-}
-
-template <bool CHECKED, bool RUNS = false>
-__device__ __forceinline__ uint32_t consume(
-    const uint8_t* __restrict__ in, uint32_t in_len, uint8_t* out, uint32_t out_cap, uint8_t* lds, uint32_t& err)
-{
-  const uint32_t lane = (uint32_t)wave::lane_id();
-  const Shared sh = shared_at(lds);
-  lzw::InRing ir;
-  lzw::OutWindow ow;
-  lzw::in_init(ir, in, in_len, lds + lzw::kOutLds);
-  lzw::out_init(ow, out, lds);
-  lzw::in_ensure(ir, ir.vbeg, ir.vbeg + lzw::kInBlock);
-  uint32_t q, total;
-  const bool preamble_ok = read_preamble(ir, q, total);
-  if (!preamble_ok || (CHECKED && total > out_cap)) {
-    err = preamble_ok ? lz::kErrOutput : lz::kErrInput;
-    if (lane == 0) {
-      wave::lds_store_release(sh.abort, 1u);
-    }
-    return 0;
-  }
-  const uint32_t limit = CHECKED ? total : out_cap;
-  uint32_t op = 0;
-  uint32_t count = 0;
-  uint32_t k = 0;
-  lzw::RunGate gate = lzw::kRunGateInit;
-  lz::Seq s;
-  s.lit_src = 0, s.lit_len = 0, s.match_off = 0, s.match_len = 0;
-  for (;;) {
-    if (count == 0) {
-      while (poll(sh.state + k) != 1) {
-        wave::nap();
-      }
-      const uint32_t* f = (const uint32_t*)(sh.slot(k) + 16);
-      s.lit_src = f[lane];
-      s.lit_len = f[64 + lane];
-      s.match_off = f[128 + lane];
-      s.match_len = f[192 + lane];
-      const uint32_t n = wave::read_lane(((const uint32_t*)sh.slot(k))[0], 0);
-      const uint32_t flags = wave::read_lane(((const uint32_t*)sh.slot(k))[1], 0);
-      wave::sync();
-      if (lane == 0) {
-        wave::lds_store_release(sh.state + k, 0u);
-      }
-      k ^= 1;
-      if (flags & kFlagBad) {
-        err |= lz::kErrInput;
-        return 0;
-      }
-      if (flags & kFlagLast) {
-        break;
-      }
-      count = n;
-      if (count == 0) {
-        continue;
-      }
-    }
-    {
-      /* the literal copies read this wave's own ring; copy elements carry no stream position */
-      const bool has_lit = lane < count && s.lit_len != 0;
-      if (wave::ballot(has_lit)) {
-        const uint32_t hi = wave::reduce_max(has_lit ? s.lit_src : 0u);
-        const uint32_t lo = ~wave::reduce_max(has_lit ? ~s.lit_src : 0u);
-        lzw::in_ensure(ir, lo, (hi & ~(lzw::kInBlock - 1)) + 2 * lzw::kInBlock);
-      }
-    }
-    bool big = false;
-    uint32_t take = 0;
-    if (RUNS && lzw::run_gate_open(gate)) {
-      bool misfit;
-      take = lzw::execute_run_batch<CHECKED>(ir, ow, limit, op, count, s, misfit);
-      gate = wave::uniform(lzw::run_gate_tried(gate, take, misfit));
-    }
-    if (take == 0) {
-      take = lzw::execute_window_batch<CHECKED>(ir, ow, limit, op, count, s, err, big);
-      if (RUNS) {
-        gate = wave::uniform(lzw::run_gate_window_took(gate, take, count));
-      }
-    }
-    if (CHECKED && err) {
-      if (lane == 0) {
-        wave::lds_store_release(sh.abort, 1u);
-      }
-      return 0;
-    }
-    if (big) {
-      /* the first sequence in hand has a long literal run or a long match, or is larger than a batch: straight to HBM */
-      if (!lzw::stream_sequence<CHECKED>(ir, ow, limit, op, wave::read_lane(s.lit_src, 0), wave::read_lane(s.lit_len, 0),
-                                         wave::read_lane(s.match_off, 0), wave::read_lane(s.match_len, 0), err)) {
-        if (lane == 0) {
-          wave::lds_store_release(sh.abort, 1u);
-        }
-        return 0;
-      }
-      /* sequence 0 and the empty sequences (the followers of its copy train) right behind it */
-      const uint64_t empty = wave::ballot(lane < count && s.lit_len + s.match_len == 0);
-      take = 1 + wave::ctz64(~(empty >> 1));
-      take = take < count ? take : count;
-    }
-    if (take < count) {
-      lzw::drop_front(s, take, count);
-    }
-    count -= take;
-  }
-  if (CHECKED && op != total) {
-    err |= lz::kErrInput;
-    return 0;
-  }
-  lzw::out_flush_all(ow, op);
-  return op;
-}
-
-} // namespace pair
 
 } // namespace snappyw

@@ -308,6 +308,41 @@ def test_corrupt_streams(backend, lz_path, oracle):
             assert status[i] != NvcompStatus.Success and actual[i] == 0
 
 
+def test_preamble_is_the_limit(backend, lz_path, oracle):
+    """What the preamble declares: a stream without a complete varint32 is malformed whatever follows; elements that end
+    short of the declared length are malformed although the capacity holds them; and a checked decode whose elements
+    overrun the declared length fails WITHOUT writing at or behind it, however much room the caller's capacity leaves
+    (every decode path takes the declared length, not the capacity, for its output limit: in a batch of the window, in a
+    streamed sequence and in the workgroup's step)."""
+    rng = np.random.RandomState(5)
+    data = rng.randint(0, 256, size=6000).astype(np.uint8).tobytes()
+    copy2 = lambda n, off: bytes([((n - 1) << 2) | 2]) + off.to_bytes(2, "little")  # noqa: E731
+    # (stream, capacity, declared length or None = malformed preamble, bytes the elements produce)
+    cases = [
+        (b"\x80", 64, None, 0),                                                     # the stream ends inside the varint
+        (b"\x80\x80\x80\x80\x80\x00" + _lit(data[:8]), 64, None, 0),                # a fifth byte that goes on
+        (b"\xff\xff\xff\xff\x1f" + _lit(data[:8]), 64, None, 0),                    # a fifth byte above 15
+        (b"\xe4\x80\x80\x80\x10" + _lit(data[:100]), 100, None, 100),               # ... whose low 32 bits are what follows
+        (_varint(1200) + _lit(data[:1000]) + 4 * copy2(50, 100), 1200, 1200, 1200),  # honest
+        (_varint(1300) + _lit(data[:1000]) + 4 * copy2(50, 100), 1300, 1300, 1200),  # the elements end short of it
+        (_varint(1000) + _lit(data[:1000]) + 4 * copy2(50, 100), 2000, 1000, 1200),  # overrun inside one batch
+        (_varint(5000) + _lit(data[:3000]) + _lit(data[3000:5000]) + copy2(60, 7), 6000, 5000, 5060),  # ... in a later one
+        (_varint(5000) + _lit(data[:4500]) + _lit(data[4500:5500]), 6000, 5000, 5500),  # ... behind a streamed literal run
+    ]
+    comp = [np.frombuffer(c[0], dtype=np.uint8) for c in cases]
+    outs, actual, status = backend.codec("Snappy").decompress(comp, [c[1] for c in cases])
+    # the size query reads the preamble alone: what it declares, 0 where it is malformed
+    assert backend.codec("Snappy").get_decompress_size(comp).tolist() == [c[2] or 0 for c in cases]
+    for i, (stream, cap, declared, produced) in enumerate(cases):
+        rc, ref = oracle.snappy_decompress(comp[i], cap)
+        if declared is not None and declared == produced:
+            assert rc == 0 and status[i] == NvcompStatus.Success and actual[i] == declared, f"case {i}"
+            assert np.array_equal(outs[i][:declared], ref)
+        else:
+            assert rc != 0 and status[i] != NvcompStatus.Success and actual[i] == 0, f"case {i}"
+            assert (outs[i][declared or 0:] == 0xA5).all(), f"case {i}: wrote behind the declared length"
+
+
 @pytest.mark.parametrize("name", ["text", "table", "float_csv", "float32", "int32", "lowcard", "zeros", "noise"])
 def test_compress_decodes_on_cpu(backend, oracle, name):
     size = 2 * 65536 + 77 if backend.name == "gpu" else 65536 + 77

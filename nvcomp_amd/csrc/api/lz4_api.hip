@@ -35,9 +35,13 @@ constexpr size_t kRunsRatio = NVCOMP_LZ4_RUNS_RATIO;
                            * (common/lz_index.hip.h). Built, parity-green and measured in round 6 (profiles/r06_token_index.json,
                            * gpurun r6e ... r6k): 26 % fewer vector instructions per launch, and SLOWER -- 494 against 643 GB/s on the
                            * headline batch: the index costs what the chase it replaces cost (built and thrown away: 500 GB/s), its
-                           * 310 wave-steps of ~55 instructions a chunk run with half the lanes idle. Off; the A/B build
-                           * lib/alt/libnvcomp_index.so and the tests keep it alive. */
+                           * 310 wave-steps of ~55 instructions a chunk run with half the lanes idle. Off.
+                           * The macro selects the INSTANTIATION of lz4w::decode_chunk (its INDEXED parameter, kIndexed below):
+                           * with 0 the window kernel holds no index code or state at all and the launch reserves no temp bytes
+                           * for one; with 1 (the A/B build lib/alt/libnvcomp_index.so, the emulator's "index" variant, the
+                           * tests) the kernel decodes through the index whenever the launch's temp buffer has room for it. */
 #endif
+constexpr bool kIndexed = NVCOMP_LZ_INDEX != 0;
 static_assert(lzl::kIndexBytesPerWave >= lzx::kScratchPerWave, "a wave's slice of the temp buffer holds its token list");
 
 /* Profiling builds only (wrong output by construction): 1 = stop after the token chase, 2 = after the parse. */
@@ -68,14 +72,17 @@ __global__ void __launch_bounds__(64 * kDecWaves, NVCOMP_LZW_WAVES_PER_SIMD) lz4
   const uint32_t w = wave::uniform(threadIdx.x >> 6);
   lzl::decode_window_loop<CHECKED>(launch, w, [&](const lzl::Chunk& c, const auto* a, uint32_t& err) -> uint32_t {
     /* the wave's slice of the temp buffer for the token index (the same for every chunk it decodes) */
-    uint8_t* index = a->index;
-    if (index != nullptr) {
-      index += ((size_t)blockIdx.x * kDecWaves + w) * lzl::kIndexBytesPerWave;
+    uint8_t* index = nullptr;
+    if constexpr (kIndexed) {
+      index = a->index;
+      if (index != nullptr) {
+        index += ((size_t)blockIdx.x * kDecWaves + w) * lzl::kIndexBytesPerWave;
+      }
     }
     if (Lz4::runs(c.in_len, c.cap)) {
-      return lz4w::decode_chunk<CHECKED, NVCOMP_LZ4W_ABLATE, true>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err, index);
+      return lz4w::decode_chunk<CHECKED, NVCOMP_LZ4W_ABLATE, true, kIndexed>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err, index);
     }
-    return lz4w::decode_chunk<CHECKED, NVCOMP_LZ4W_ABLATE, false>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err, index);
+    return lz4w::decode_chunk<CHECKED, NVCOMP_LZ4W_ABLATE, false, kIndexed>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err, index);
   });
 }
 

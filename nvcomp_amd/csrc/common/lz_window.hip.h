@@ -75,6 +75,22 @@ constexpr uint32_t kInLds = kInRing + 16; /* first 16 bytes mirrored after the e
 #ifndef NVCOMP_LZW_ABLATE_EXEC
 #define NVCOMP_LZW_ABLATE_EXEC 0
 #endif
+/* The initial value of a register that is written under a condition and read only where that condition held (the far
+ * matches' data: loaded by far lanes, stored by far lanes). On the device: whatever the register holds -- an empty asm
+ * statement "defines" it, no instruction is issued; a literal 0 was a v_mov per register and batch (and the compiler turns
+ * __builtin_nondeterministic_value into the same zeros). The host build of the emulator (tests/emu) keeps zeros: its
+ * sanitizer runs want defined values. */
+#if defined(__HIPCC__)
+__device__ __forceinline__ uint32_t unset_u32()
+{
+  uint32_t v;
+  asm volatile("" : "=v"(v)); /* volatile: every use is a register of its own, not copies of one */
+  return v;
+}
+#define LZW_UNSET_U32 lzw::unset_u32()
+#else
+#define LZW_UNSET_U32 0u
+#endif
 #ifndef NVCOMP_LZW_CHASE_ENOUGH
 #define NVCOMP_LZW_CHASE_ENOUGH 64 /* tokens in hand from which the chase does not open another window (A/B: 40, 48) */
 #endif
@@ -583,13 +599,21 @@ __device__ __forceinline__ uint32_t ld32(const uint8_t* p)
 }
 
 /* Number of 4-byte steps (2, 4 or 8) that cover the longest participating run:
- * two ballots instead of a wave-wide max reduction. */
-__device__ __forceinline__ uint32_t steps_for(bool participates, uint32_t len)
+ * two ballots instead of a wave-wide max reduction.
+ * A ballot of ONE compare is the compare itself (v_cmp writes the mask). A ballot of `a && b` is not: the compiler forms
+ * the mask on the scalar side (s_and_b64), turns it into a 0 / 1 register (v_cndmask) and compares that with 0 (v_cmp_ne)
+ * -- two vector instructions for a mask the scalar unit already held. So the masks of this file are ballots of single
+ * compares, joined with & | ~ on the scalar unit; `participants` is such a mask. */
+__device__ __forceinline__ uint32_t steps_for(uint64_t participants, uint32_t len)
 {
-  if (wave::ballot(participates && len > 16)) {
+  if (wave::ballot(len > 16) & participants) {
     return 8;
   }
-  return wave::ballot(participates && len > 8) ? 4u : 2u;
+  return (wave::ballot(len > 8) & participants) ? 4u : 2u;
+}
+__device__ __forceinline__ uint32_t steps_for(bool participates, uint32_t len)
+{
+  return steps_for(wave::ballot(participates), len);
 }
 
 /* Note on alignment: a ds_read_b32 / ds_write_b32 with any misaligned lane serialises the wave instruction
@@ -611,6 +635,27 @@ __device__ __forceinline__ void copy_dwords_clamped(uint8_t* dst, const uint8_t*
   for (uint32_t i = 0; i < STEPS; ++i) {
     const uint32_t o = 4 * i < last ? 4 * i : last;
     lz::st_u32(dst + o, lz::ld_u32(src + o));
+  }
+}
+
+/* The same for ranges that do not overlap (a literal run: ring -> window): every load is issued before the first store, so
+ * the run costs one LDS round trip, and the dwords live in an array of this instantiation alone. (One array filled and
+ * stored under `if (i < steps)` for a run-time `steps` travelled through the arms of that ladder: 5 v_mov_b32 and 8
+ * v_mov_b64 per batch.) */
+template <uint32_t STEPS>
+__device__ __forceinline__ void copy_dwords_clamped_disjoint(uint8_t* dst, const uint8_t* src, uint32_t len)
+{
+  const uint32_t last = len - 4;
+  uint32_t data[STEPS];
+#pragma unroll
+  for (uint32_t i = 0; i < STEPS; ++i) {
+    const uint32_t o = 4 * i < last ? 4 * i : last;
+    data[i] = lz::ld_u32(src + o);
+  }
+#pragma unroll
+  for (uint32_t i = 0; i < STEPS; ++i) {
+    const uint32_t o = 4 * i < last ? 4 * i : last;
+    lz::st_u32(dst + o, data[i]);
   }
 }
 
@@ -1614,8 +1659,8 @@ __device__ __forceinline__ uint32_t execute_window_batch(
   /* leading sequences whose cumulative output fits one batch (a length is < 2^31: the first sum above kBatchMax has
    * not wrapped, whatever the sums behind it do) */
   /* ... and a sequence with a long literal run or a long match is not for the window at all (stream_sequence) */
-  const bool streamed = !RING_LITERALS && (s.lit_len >= kStreamLit || s.match_len >= kStreamMatch);
-  const uint64_t over = wave::ballot(incl > kBatchMax || streamed);
+  const uint64_t over = wave::ballot(incl > kBatchMax)
+                        | (RING_LITERALS ? 0ull : wave::ballot(s.lit_len >= kStreamLit) | wave::ballot(s.match_len >= kStreamMatch));
   uint32_t take = over ? wave::ctz64(over) : 64u;
   take = take < n ? take : n;
   if (take == 0) {
@@ -1633,7 +1678,7 @@ __device__ __forceinline__ uint32_t execute_window_batch(
     /* the sums grow with the lane: the batch's end is the only output test (op <= out_cap <= 2^26, total <= kBatchMax);
      * offset 0 wraps to the largest value, so one compare covers "0 or beyond the produced output" */
     const bool bad_out = op + total > out_cap;
-    const uint64_t any_off = wave::ballot(my_match != 0 && s.match_off - 1 >= match_dst);
+    const uint64_t any_off = wave::ballot(my_match != 0) & wave::ballot(s.match_off - 1 >= match_dst);
     if (bad_out || any_off) {
       err |= (bad_out ? lz::kErrOutput : 0u) | (any_off ? lz::kErrOffset : 0u);
       return 0;
@@ -1657,26 +1702,37 @@ __device__ __forceinline__ uint32_t execute_window_batch(
    * copies, one after the other, they were 18 % of that decoder's time (phase clock, profiles/archive/r03_deflate_phases.json) */
   constexpr uint32_t kMinShort = RING_LITERALS ? 3 : 4;
   const bool short_match = my_match - kMinShort <= kMatchShort - kMinShort; /* kMinShort .. kMatchShort */
-  const bool is_near = my_match != 0 && match_src >= ow.valid_lo;
   /* the data comes with one or two 16-byte loads, which must stay inside the chunk's buffer (a source in the last 32
    * bytes of the buffer, or a wrapped one of a corrupt unchecked stream, takes the cooperative path below) */
   const bool far_lane = short_match && match_src + my_match <= ow.flushed && out_cap >= 32 && match_src <= out_cap - 32;
-  uint32_t far_l4 = 0;
-  uint32_t far_data[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const uint32_t far_steps = steps_for(far_lane, my_match);
+  /* the same as masks (the compares are the ones above) */
+  const uint64_t match_mask = wave::ballot(my_match != 0);
+  const uint64_t short_mask = wave::ballot(my_match - kMinShort <= kMatchShort - kMinShort);
+  const uint64_t far_mask = out_cap >= 32 ? short_mask & wave::ballot(match_src + my_match <= ow.flushed)
+                                                & wave::ballot(match_src <= out_cap - 32)
+                                          : 0ull;
+  /* (no zero fill: far_store_aligned stores nothing of a lane that is not `on`, and of a match of up to 16 bytes nothing
+   * that comes from far_data[4..7] -- the dword it may take from there is shifted out by align_bytes) */
+  uint32_t far_l4 = LZW_UNSET_U32;
+  uint32_t far_data[8] = {LZW_UNSET_U32, LZW_UNSET_U32, LZW_UNSET_U32, LZW_UNSET_U32,
+                          LZW_UNSET_U32, LZW_UNSET_U32, LZW_UNSET_U32, LZW_UNSET_U32};
+  const uint32_t far_steps = steps_for(far_mask, my_match);
   if (far_lane && !(NVCOMP_LZW_ABLATE_EXEC & 2)) {
 #ifdef NVCOMP_LZW_FAR_ABLATE /* profiling builds only (wrong output): far reads folded onto the chunk's first KiB */
-    const uint8_t* src = ow.out + (match_src & 1023u);
+    const uint32_t src_at = match_src & 1023u;
 #else
-    const uint8_t* src = ow.out + match_src;
+    const uint32_t src_at = match_src;
 #endif
+    /* every address is the chunk's (uniform) base plus a 32-bit lane offset: the loads take the scalar-base form, no
+     * 64-bit address is built per lane (src_at + my_match <= flushed <= out_cap < 2^31: the sums do not wrap) */
+    const uint8_t* src = ow.out + src_at;
     /* A scattered load costs the CU's address unit a slot per lane whatever its width (profiles/archive/r02_decode_phases.json:
      * issuing 3-9 dword loads per batch was 11 % of the wave's time): 16 bytes per load, two loads at most, plus the
      * match's last dword. */
     const wave::u32x4 f0 = wave::gload_u32x4(src);
     far_data[0] = f0.x, far_data[1] = f0.y, far_data[2] = f0.z, far_data[3] = f0.w;
     if (my_match > 16) {
-      const wave::u32x4 f1 = wave::gload_u32x4(src + 16);
+      const wave::u32x4 f1 = wave::gload_u32x4(ow.out + (src_at + 16u));
       far_data[4] = f1.x, far_data[5] = f1.y, far_data[6] = f1.z, far_data[7] = f1.w;
     }
     /* the match's last four bytes; of a three-byte match: a byte that is never used, then its three */
@@ -1691,7 +1747,7 @@ __device__ __forceinline__ uint32_t execute_window_batch(
       far_l4 = RING_LITERALS && my_match < 4 ? f0.x << 8 : wave::align_bytes(hi, lo, d & 3u);
     }
 #else
-    far_l4 = RING_LITERALS && my_match < 4 ? f0.x << 8 : wave::gload_u32(src + my_match - 4);
+    far_l4 = RING_LITERALS && my_match < 4 ? f0.x << 8 : wave::gload_u32(ow.out + (src_at + my_match - 4u));
 #endif
   }
 
@@ -1703,25 +1759,31 @@ __device__ __forceinline__ uint32_t execute_window_batch(
      * range wraps to a huge value: one compare) */
     const bool lit_own = my_lit - 1 < kLitShort && s.lit_src - ir.lo + my_lit <= ir.hi - ir.lo;
     const bool lit_lane = lit_own && my_lit >= 4;
-    /* the ring wraps at kInRing; its 16-byte mirror covers a dword that starts before the end,
-     * and a run crossing the end is split by the modulo per step */
-    const uint32_t lit_steps = steps_for(lit_lane, my_lit);
-    if (lit_lane) {
-      const uint32_t last = my_lit - 4;
-      uint32_t data[8];
-#pragma unroll
-      for (uint32_t i = 0; i < 8; ++i) {
-        if (i < lit_steps) {
-          const uint32_t o = 4 * i < last ? 4 * i : last;
-          data[i] = ld32(ir.ring + ((s.lit_src + o) & (kInRing - 1)));
+    /* the ring wraps at kInRing; its 16-byte mirror covers a dword that starts before the end. A run that ends inside
+     * the mirror is read from ONE base address (clamped offsets added, as everywhere); only when some lane's run goes on
+     * behind the mirror -- one run in a hundred -- the wave takes the loop that wraps every step's address by itself. */
+    const uint64_t own_mask = wave::ballot(my_lit - 1 < kLitShort) & wave::ballot(s.lit_src - ir.lo + my_lit <= ir.hi - ir.lo);
+    const uint64_t word_mask = wave::ballot(my_lit >= 4);
+    const uint32_t lit_steps = steps_for(own_mask & word_mask, my_lit);
+    const uint32_t lit_at = s.lit_src & (kInRing - 1);
+    const uint64_t lit_wraps = wave::ballot(lit_at + my_lit > kInRing + 16) & own_mask & word_mask;
+    if (lit_wraps == 0) {
+      if (lit_lane) {
+        const uint8_t* src = ir.ring + lit_at;
+        if (lit_steps == 2) {
+          copy_dwords_clamped_disjoint<2>(dst, src, my_lit);
+        } else if (lit_steps == 4) {
+          copy_dwords_clamped_disjoint<4>(dst, src, my_lit);
+        } else {
+          copy_dwords_clamped_disjoint<8>(dst, src, my_lit);
         }
       }
-#pragma unroll
-      for (uint32_t i = 0; i < 8; ++i) {
-        if (i < lit_steps) {
-          const uint32_t o = 4 * i < last ? 4 * i : last;
-          lz::st_u32(dst + o, data[i]);
-        }
+    } else if (lit_lane) {
+      const uint32_t last = my_lit - 4;
+#pragma unroll 1
+      for (uint32_t i = 0; i < lit_steps; ++i) {
+        const uint32_t o = 4 * i < last ? 4 * i : last;
+        lz::st_u32(dst + o, ld32(ir.ring + ((s.lit_src + o) & (kInRing - 1))));
       }
     }
     LZW_T(6); /* literal runs of 4..32 bytes */
@@ -1729,7 +1791,7 @@ __device__ __forceinline__ uint32_t execute_window_batch(
      * measured 5 % slower on the headline: a misaligned LDS store costs a cycle or two per ACTIVE lane, and 30 % of the
      * sequences have such a run, 10 % one of four bytes or more) */
     const bool lit_tiny = lit_own && my_lit < 4;
-    if (wave::ballot(lit_tiny)) {
+    if (own_mask & ~word_mask) {
       if (lit_tiny) {
         dst[0] = ir.ring[s.lit_src & (kInRing - 1)];
         if (my_lit > 1) {
@@ -1741,7 +1803,7 @@ __device__ __forceinline__ uint32_t execute_window_batch(
       }
     }
     LZW_T(12); /* literal runs of 1..3 bytes */
-    uint64_t pending = wave::ballot(my_lit != 0 && !lit_own);
+    uint64_t pending = wave::ballot(my_lit != 0) & ~own_mask;
     LZ_STAT("lit_lanes", wave::popc64(wave::ballot(lit_own)));
     LZ_STAT("lit_coop", wave::popc64(pending));
     while (pending) {
@@ -1765,7 +1827,7 @@ __device__ __forceinline__ uint32_t execute_window_batch(
 
   LZW_T(13); /* long literal runs, whole wave */
   /* ---- far match data into the window ---- */
-  if (wave::ballot(far_lane) && !(NVCOMP_LZW_ABLATE_EXEC & 16)) {
+  if (far_mask && !(NVCOMP_LZW_ABLATE_EXEC & 16)) {
     uint8_t* dst = out_at(ow, far_lane ? match_dst : ow.wbase);
     if (far_steps == 2) {
       far_store_aligned<2>(dst, far_data, far_l4, my_match, far_lane);
@@ -1781,15 +1843,15 @@ __device__ __forceinline__ uint32_t execute_window_batch(
 
   /* ---- remaining matches, oldest first: multi-round resolution in LDS ---- */
   {
-    const bool near_lane = is_near && short_match && s.match_off >= 4;
-    uint64_t pending = (NVCOMP_LZW_ABLATE_EXEC & 8) ? 0ull : wave::ballot(my_match != 0 && !far_lane);
-    const uint64_t near_mask = wave::ballot(near_lane);
+    /* near: a short match with a period of 4 or more whose source the window holds */
+    uint64_t pending = (NVCOMP_LZW_ABLATE_EXEC & 8) ? 0ull : match_mask & ~far_mask;
+    const uint64_t near_mask = match_mask & short_mask & wave::ballot(match_src >= ow.valid_lo) & wave::ballot(s.match_off >= 4);
     LZ_STAT("match_far_lanes", wave::popc64(wave::ballot(far_lane)));
     LZ_STAT("match_near_lanes", wave::popc64(near_mask));
     LZ_STAT("match_coop", wave::popc64(pending & ~near_mask));
     LZ_STAT("match_coop_below_4", wave::popc64(wave::ballot(my_match != 0 && my_match < 4)));
     LZ_STAT("match_coop_long", wave::popc64(wave::ballot(my_match > kMatchShort)));
-    LZ_STAT("match_coop_short_period", wave::popc64(wave::ballot(is_near && short_match && s.match_off < 4)));
+    LZ_STAT("match_coop_short_period", wave::popc64(wave::ballot(my_match != 0 && match_src >= ow.valid_lo && short_match && s.match_off < 4)));
     while (pending) {
       const uint32_t f = wave::ctz64(pending);
       const uint32_t hw = wave::read_lane(match_dst, f); /* every byte below hw is final */
@@ -1802,8 +1864,11 @@ __device__ __forceinline__ uint32_t execute_window_batch(
         LZW_T(14); /* matches copied by the whole wave */
         continue;
       }
-      const bool ready = near_lane && wave::lane_in(pending) && (lane == f || match_src + my_match <= hw);
-      const uint32_t steps = steps_for(ready, my_match);
+      /* ready: a pending near lane whose source is final -- and the oldest one, whatever its source (it overlaps only
+       * itself) */
+      const uint64_t ready_mask = near_mask & pending & (wave::ballot(match_src + my_match <= hw) | (1ull << f));
+      const bool ready = wave::lane_in(ready_mask);
+      const uint32_t steps = steps_for(ready_mask, my_match);
       LZ_STAT("mrr_rounds", 1);
       LZ_STAT("mrr_iters", steps);
       if (ready) {
@@ -1821,7 +1886,7 @@ __device__ __forceinline__ uint32_t execute_window_batch(
         }
       }
       wave::sync();
-      pending &= ~wave::ballot(ready);
+      pending &= ~ready_mask;
     }
   }
 

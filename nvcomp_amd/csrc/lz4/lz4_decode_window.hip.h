@@ -15,6 +15,8 @@
 #include "common/lz_window.hip.h"
 #include "common/lz_index.hip.h"
 
+#include <type_traits>
+
 namespace lz4w {
 
 using lzw::kUnknown;
@@ -295,7 +297,9 @@ __device__ __forceinline__ void parse_batch(const R& r, uint32_t p, uint32_t fro
   s.match_off = mine ? ((uint32_t)x & 0xffffu) : 0;
   s.match_len = mine ? mcode + 4 + (mcode == 15 ? mext : 0u) : 0;
   bad = false;
-  const uint64_t rest = wave::ballot(active && !straight);
+  /* (a mask of single compares joined on the scalar unit: common/lz_window.hip.h, steps_for) */
+  const uint64_t rest = wave::ballot(lane - from < to - from)
+                        & (wave::ballot(lit2) | wave::ballot(n255 >= 6) | wave::ballot(p < r.lo) | wave::ballot(q + 8 >= lim));
   if (rest) {
     lz::Seq g;
     bool gbad;
@@ -376,6 +380,10 @@ struct FrontEnd
   static __device__ __forceinline__ uint32_t streamed_take(const lz::Seq&, uint32_t) { return 1; }
 };
 
+struct NoIndex
+{
+};
+
 /* Decode one chunk with the calling wave; `lds` is this wave's kLdsPerWave bytes. */
 /* ABLATE (profiling builds only, results are wrong by construction): 1 = stop after the
  * token chase, 2 = after the parse, 0 = the real decoder. */
@@ -383,7 +391,11 @@ struct FrontEnd
  * other kind of data 1.5-2 % (block placement and register allocation of the batch executor around it: gpurun r6u, r6v --
  * the same with the attempts gated off at run time), so the kernels instantiate the loop twice and pick per chunk by what
  * the stream shrank to (decode_one: runs only pay from 8 x on). */
-template <bool CHECKED, int ABLATE = 0, bool RUNS = false>
+/* INDEXED: the sequences' positions come from the token index (common/lz_index.hip.h) as far as it reaches. A property of
+ * the instantiation, not of the call: with `index_scratch` tested at run time the loop of every build kept the index's
+ * reader, its branches and the three registers settle() holds across the far-match wait (928 of 5 591 vector instructions
+ * of the kernel, 12 of 18 SGPR spills). false: no Index object exists and index_scratch is not looked at. */
+template <bool CHECKED, int ABLATE = 0, bool RUNS = false, bool INDEXED = false>
 __device__ __forceinline__ uint32_t decode_chunk(
     const uint8_t* __restrict__ in, uint32_t in_len, uint8_t* out, uint32_t out_cap, uint8_t* lds, uint32_t& err,
     uint8_t* index_scratch = nullptr)
@@ -398,17 +410,23 @@ __device__ __forceinline__ uint32_t decode_chunk(
    * built in the LDS that the ring, the window and the jump tables use afterwards. */
   static_assert(lzx::kLdsBytes <= lzw::kLdsPerWave, "the index is built in the wave's own LDS");
   LZW_T(9);
-  lzx::Index ix = lzx::build<IndexFormat>(in, in_len, lds, index_scratch);
-  LZW_T(15); /* the token index */
+  /* (an empty object when !INDEXED: nothing of it is read below) */
+  std::conditional_t<INDEXED, lzx::Index, NoIndex> ix;
+  uint32_t resume = 0;
+  if constexpr (INDEXED) {
+    ix = lzx::build<IndexFormat>(in, in_len, lds, index_scratch);
+    LZW_T(15); /* the token index */
 #ifdef NVCOMP_LZX_BUILD_ONLY /* profiling builds only: the index is built and thrown away (what the walk costs in place) */
-  ix.lanes = 0, ix.ahead_n = 0, ix.resume = 0;
+    ix.lanes = 0, ix.ahead_n = 0, ix.resume = 0;
 #endif
+    resume = ix.resume;
+  }
   lzw::InRing ir;
   lzw::OutWindow ow;
   lzw::in_init(ir, in, in_len, lds + lzw::kOutLds);
   lzw::out_init(ow, out, lds);
   lzw::Chase c;
-  lzw::chase_init(c, ir.vbeg + ix.resume, lds + lzw::kOutLds + lzw::kInLds);
+  lzw::chase_init(c, ir.vbeg + resume, lds + lzw::kOutLds + lzw::kInLds);
   uint32_t op = 0;
   uint32_t seqpos = 0;
   uint32_t count = 0; /* sequences recorded in seqpos lanes [0, count) and not yet executed */
@@ -429,22 +447,27 @@ __device__ __forceinline__ uint32_t decode_chunk(
   s.match_off = 0;
   s.match_len = 0;
   for (;;) {
-    const bool indexed = lzx::more(ix);
+    bool indexed = false;
+    if constexpr (INDEXED) {
+      indexed = lzx::more(ix);
+    }
     if (count == 0 && !indexed && c.q >= ir.vend) {
       break;
     }
     uint32_t before = NVCOMP_LZ4W_KEEP_PARSED ? count : 0u; /* lanes [before, count) are parsed this round */
     const bool refill = count < kRefillBelow && (indexed || c.q < ir.vend);
     if (refill && indexed) {
-      /* the next token positions out of the index */
-      LZW_T(10);
-      count = lzx::read(ix, seqpos, count, ir.vbeg);
-      if (count == 0) {
-        continue; /* (the lists that were left held nothing: the chase takes over) */
+      if constexpr (INDEXED) {
+        /* the next token positions out of the index */
+        LZW_T(10);
+        count = lzx::read(ix, seqpos, count, ir.vbeg);
+        if (count == 0) {
+          continue; /* (the lists that were left held nothing: the chase takes over) */
+        }
+        const uint32_t oldest = wave::read_lane(seqpos, 0);
+        lzw::in_ensure(ir, oldest, (oldest & ~(lzw::kInBlock - 1)) + 3 * lzw::kInBlock);
+        LZW_T(0);
       }
-      const uint32_t oldest = wave::read_lane(seqpos, 0);
-      lzw::in_ensure(ir, oldest, (oldest & ~(lzw::kInBlock - 1)) + 3 * lzw::kInBlock);
-      LZW_T(0);
     } else if (refill) {
       /* keep the stream resident from the oldest unexecuted token to well past the chase */
       const uint32_t oldest = count ? wave::read_lane(seqpos, 0) : c.q;
@@ -486,7 +509,11 @@ __device__ __forceinline__ uint32_t decode_chunk(
       gate = wave::uniform(lzw::run_gate_tried(gate, take, misfit));
     }
     if (take == 0) {
-      auto settle = [&ix]() { lzx::settle(ix); };
+      auto settle = [&]() {
+        if constexpr (INDEXED) {
+          lzx::settle(ix);
+        }
+      };
       take = lzw::execute_window_batch<CHECKED, false, decltype(settle), NVCOMP_LZW_LAZY_FLUSH && !RUNS>(ir, ow, out_cap, op, count, s, err, big, settle);
       if (CHECKED && err) {
         return 0;

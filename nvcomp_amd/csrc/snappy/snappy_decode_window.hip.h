@@ -229,7 +229,8 @@ __device__ __forceinline__ bool parse_fast(
   const uint64_t c = is_lit ? y : w;
   const uint32_t tag = (uint32_t)c & 0xffu;
   const uint32_t k = tag & 3u;
-  if (wave::ballot(active && is_lit && code >= 60)) {
+  /* (a mask of single compares joined on the scalar unit: common/lz_window.hip.h, steps_for) */
+  if (wave::ballot(lane - from < to - from) & wave::ballot((t & 3u) == 0) & wave::ballot(code >= 60)) {
     return false;
   }
   const bool has_copy = k != 0; /* a literal element behind a literal element is a token of its own */
@@ -275,7 +276,8 @@ __device__ __forceinline__ uint64_t merge_trains(lz::Seq& s, uint32_t count)
   const uint32_t prev_off = wave::prev_lane(s.match_off);
   const uint32_t prev_len = wave::prev_lane(s.match_len);
   const bool cont = s.lit_len == 0 && s.match_len != 0 && prev_len != 0 && prev_off == s.match_off;
-  const uint64_t train = wave::ballot(cont);
+  const uint64_t train = wave::ballot(s.lit_len == 0) & wave::ballot(s.match_len != 0) & wave::ballot(prev_len != 0)
+                         & wave::ballot(prev_off == s.match_off);
   if (train) {
     const uint32_t incl = wave::scan_add_inclusive(lane < count ? s.match_len : 0u);
     const uint64_t above = lane < 63 ? train >> (lane + 1) : 0ull;

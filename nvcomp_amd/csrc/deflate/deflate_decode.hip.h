@@ -1024,6 +1024,10 @@ __device__ __forceinline__ uint32_t decode_chunk(
           const uint32_t k = (dsym >> 1) - 1;
           dist = ((2 + (dsym & 1u)) << k) + 1 + b.take(k);
         }
+        if (SIZE_ONLY && dist > f.produced + f.run) { /* in front of the first byte: the executor says so when it decodes */
+          bad = true;
+          break;
+        }
         close_sequence<SIZE_ONLY>(f, mlen, dist);
       }
       LZW_T(10);

@@ -9,6 +9,7 @@ import zlib
 import numpy as np
 import pytest
 
+from deflate_streams import BitWriter
 from nvcomp_amd import datasets
 from nvcomp_amd._lib import NvcompStatus
 
@@ -127,32 +128,6 @@ def test_ragged_and_tiny_chunks(backend):
               text[:31999], rng.randint(0, 256, 70, dtype=np.uint8), np.zeros(65536, np.uint8)]
     for level in (9, 0):
         check(backend, "Deflate", chunks, [raw_deflate(c, level) for c in chunks], comp_align=1, out_align=1, base_misalign=3)
-
-
-class BitWriter:
-    """LSB-first bit packing of RFC 1951; Huffman codes go in most significant bit first."""
-
-    def __init__(self):
-        self.bits = []
-
-    def put(self, value, n, msb_first=False):
-        for i in range(n):
-            self.bits.append((value >> (n - 1 - i if msb_first else i)) & 1)
-
-    def align(self):
-        while len(self.bits) % 8:
-            self.bits.append(0)
-
-    def raw(self, data):
-        assert len(self.bits) % 8 == 0
-        for byte in data:
-            self.put(byte, 8)
-
-    def bytes(self):
-        out = bytearray((len(self.bits) + 7) // 8)
-        for i, b in enumerate(self.bits):
-            out[i // 8] |= b << (i % 8)
-        return bytes(out)
 
 
 def test_longest_matches_and_farthest_distances(backend):

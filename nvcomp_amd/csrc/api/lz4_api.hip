@@ -23,9 +23,6 @@ using lzl::kDecWaves;
 using lzl::kEncWaves;
 using lzl::kWideWaves;
 
-#ifndef NVCOMP_LZ4_PAIR_RUNS
-#define NVCOMP_LZ4_PAIR_RUNS 0 /* the two-wave kernel's consumer with the run executor (A/B) */
-#endif
 #ifndef NVCOMP_LZ4_RUNS_RATIO
 #define NVCOMP_LZ4_RUNS_RATIO 8
 #endif
@@ -44,16 +41,11 @@ constexpr size_t kRunsRatio = NVCOMP_LZ4_RUNS_RATIO;
 constexpr bool kIndexed = NVCOMP_LZ_INDEX != 0;
 static_assert(lzl::kIndexBytesPerWave >= lzx::kScratchPerWave, "a wave's slice of the temp buffer holds its token list");
 
-/* Profiling builds only (wrong output by construction): 1 = stop after the token chase, 2 = after the parse. */
-#ifndef NVCOMP_LZ4W_ABLATE
-#define NVCOMP_LZ4W_ABLATE 0
-#endif
-
 /* LZ4 as common/lz_api.hip.h sees it. */
 struct Lz4
 {
   using FrontEnd = lz4w::FrontEnd;
-  static constexpr bool kPairRuns = NVCOMP_LZ4_PAIR_RUNS != 0;
+  static constexpr bool kPairRuns = false; /* the runs of a typed column go to alone() */
   static constexpr bool kEmptyIsError = false;
   /* a chunk that shrank 8 x or more (by the caller's capacity: an LZ4 block does not say what it decodes to) takes the
    * instance of the loop that tries the run executor; everything else the one without it (lz4w::decode_chunk) */
@@ -61,7 +53,7 @@ struct Lz4
   template <bool CHECKED>
   static __device__ __forceinline__ uint32_t alone(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint8_t* lds, uint32_t& err)
   {
-    return lz4w::decode_chunk<CHECKED, 0, true>(in, n, out, cap, lds, err, nullptr);
+    return lz4w::decode_chunk<CHECKED, true>(in, n, out, cap, lds, err, nullptr);
   }
 };
 
@@ -80,9 +72,9 @@ __global__ void __launch_bounds__(64 * kDecWaves, NVCOMP_LZW_WAVES_PER_SIMD) lz4
       }
     }
     if (Lz4::runs(c.in_len, c.cap)) {
-      return lz4w::decode_chunk<CHECKED, NVCOMP_LZ4W_ABLATE, true, kIndexed>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err, index);
+      return lz4w::decode_chunk<CHECKED, true, kIndexed>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err, index);
     }
-    return lz4w::decode_chunk<CHECKED, NVCOMP_LZ4W_ABLATE, false, kIndexed>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err, index);
+    return lz4w::decode_chunk<CHECKED, false, kIndexed>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err, index);
   });
 }
 
@@ -304,11 +296,7 @@ nvcompStatus_t nvcompBatchedLZ4CompressAsync(
   case NVCOMP_TYPE_INT:
   case NVCOMP_TYPE_UINT: return lzl::compress_async<lz4_compress_kernel<4>, kEncWaves>(call);
   default:
-#if NVCOMP_LZM_WIDE
     return lzl::compress_async<lz4_compress_wide_kernel, kWideWaves>(call);
-#else
-    return lzl::compress_async<lz4_compress_kernel<1>, kEncWaves>(call);
-#endif
   }
 }
 

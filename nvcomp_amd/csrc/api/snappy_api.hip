@@ -23,9 +23,6 @@ using lzl::kDecWaves;
 using lzl::kEncWaves;
 using lzl::kWideWaves;
 
-#ifndef NVCOMP_SNAPPY_RUNS
-#define NVCOMP_SNAPPY_RUNS 1 /* A/B: 0 = no run executor in the Snappy decoder */
-#endif
 #ifndef NVCOMP_SNAPPY_RUNS_RATIO
 #define NVCOMP_SNAPPY_RUNS_RATIO 8
 #endif
@@ -40,7 +37,7 @@ struct Snappy
   /* a chunk that shrank 8 x or more takes the instance of the loop that tries the run executor (snappyw::decode_chunk) */
   static __device__ __forceinline__ bool runs(size_t in_len, size_t cap)
   {
-    return NVCOMP_LZW_RUNS && NVCOMP_SNAPPY_RUNS && in_len * kRunsRatio <= cap;
+    return NVCOMP_LZW_RUNS && in_len * kRunsRatio <= cap;
   }
   template <bool CHECKED>
   static __device__ __forceinline__ uint32_t alone(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint8_t* lds, uint32_t& err)
@@ -88,6 +85,9 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) snappy_decompress_size_ke
   });
 }
 
+/* The one-window compressor (common/lz_match.hip.h). No call launches it since untyped data -- all of Snappy's -- takes the
+ * wide steps below (its A/B switch is retired: DESIGN.md, "retired switches"). It is still compiled: without it in the
+ * module the compiler writes one condition of snappy_compress_wide_kernel differently (profiles/lz_switches_retired.md). */
 __global__ void __launch_bounds__(64 * kEncWaves, NVCOMP_LZM_WAVES_PER_SIMD) snappy_compress_kernel(const lzl::CompressLaunch launch)
 {
   __shared__ uint16_t tables[kEncWaves][lzm::kTableU16];
@@ -206,11 +206,7 @@ nvcompStatus_t nvcompBatchedSnappyCompressAsync(
   const lzl::CompressCall call = {"Snappy", snappy_opts_status(format_opts, max_uncompressed_chunk_bytes), device_uncompressed_ptrs,
                                   device_uncompressed_bytes, max_uncompressed_chunk_bytes, batch_size, device_temp_ptr, temp_bytes,
                                   device_compressed_ptrs, device_compressed_bytes, stream};
-#if NVCOMP_LZM_WIDE
   return lzl::compress_async<snappy_compress_wide_kernel, kWideWaves>(call);
-#else
-  return lzl::compress_async<snappy_compress_kernel, kEncWaves>(call);
-#endif
 }
 
 } // extern "C"

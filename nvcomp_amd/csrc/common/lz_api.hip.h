@@ -29,10 +29,8 @@
 #ifndef NVCOMP_LZM_WAVES_PER_BLOCK
 #define NVCOMP_LZM_WAVES_PER_BLOCK 4
 #endif
-/* Untyped data takes the 256-position steps of common/lz_match_wide.hip.h (0: the one-window compressor, A/B build). */
-#ifndef NVCOMP_LZM_WIDE
-#define NVCOMP_LZM_WIDE 1
-#endif
+/* Untyped data takes the 256-position steps of common/lz_match_wide.hip.h; typed data (2- and 4-byte elements) the
+ * one-window compressor of common/lz_match.hip.h. */
 #ifndef NVCOMP_LZMW_WAVES_PER_BLOCK
 #define NVCOMP_LZMW_WAVES_PER_BLOCK 1
 #endif
@@ -141,7 +139,7 @@ __device__ __forceinline__ void decode_pair(const Batch& b, uint8_t* lds)
    * producer and consumer (4 096 chunks of the sorted-key column: 840 GB/s here, 5 120 chunks in the persistent kernel:
    * 3 850). That loop's registers cost this kernel its eighth wave per SIMD (common/lz_launch.hip.h: the mix does not mind). */
   static_assert(lzw::kLdsPerWave <= lzw::pair::kLdsPerChunk, "the lone wave's LDS is the pair's");
-  const bool solo = NVCOMP_LZ_PAIR_SOLO && work && Format::runs(c.in_len, c.cap);
+  const bool solo = work && Format::runs(c.in_len, c.cap);
   if (w == 0) {
     if (work && !solo) {
       lzw::pair::produce<typename Format::FrontEnd, CHECKED>(c.in, (uint32_t)c.in_len, lds);
@@ -186,7 +184,7 @@ __device__ __forceinline__ void decode_team_loop(const Launch& launch, uint8_t* 
           [](uint32_t role, const uint8_t* i, uint32_t n, uint8_t* o, uint32_t cap, uint8_t* scratch, uint32_t& e) -> uint32_t {
             /* the team's fallback is the two-wave kernel: chunks that shrank 8 x (here: mostly the 16 x ones of the team's
              * own test) are runs -- one wave with the loop that holds the run executor */
-            const bool solo = NVCOMP_LZ_PAIR_SOLO && Format::runs(n, cap);
+            const bool solo = Format::runs(n, cap);
             if (role == 0) {
               if (!solo) {
                 lzw::pair::produce<typename Format::FrontEnd, true>(i, n, scratch);
@@ -272,17 +270,17 @@ __device__ __forceinline__ void compress_loop(const CompressLaunch& launch, uint
 
 /* ---- host side ---- */
 
-/* Launch Kernel over a batch, `places` chunks per workgroup at a time. Persistent when `allow` and the caller's temp buffer
+/* Launch Kernel over a batch, `places` chunks per workgroup at a time. Persistent when the caller's temp buffer
  * can hold the ticket counter: as many workgroups as stay resident (at most `max_per_cu` per CU; 0: no cap), the rest of
  * the batch by ticket. Otherwise one place per chunk, statically. make_args(ticket, first_dynamic) -> the kernel's parameter. */
 template <auto Kernel, class MakeArgs>
 static inline void launch_persistent(
     hipStream_t stream, void* temp, size_t temp_bytes, size_t batch_size, unsigned places, unsigned block_threads,
-    int max_per_cu, bool allow, MakeArgs make_args)
+    int max_per_cu, MakeArgs make_args)
 {
   unsigned groups = (unsigned)((batch_size + places - 1) / places);
   uint32_t* ticket = nullptr;
-  if (allow && temp != nullptr && temp_bytes >= sizeof(uint32_t) && ((uintptr_t)temp & 3u) == 0) {
+  if (temp != nullptr && temp_bytes >= sizeof(uint32_t) && ((uintptr_t)temp & 3u) == 0) {
     static ResidentCache resident; /* per kernel; inside, per device ordinal */
     const unsigned fit = resident.get(Kernel, block_threads, max_per_cu);
     if (fit != 0 && fit < groups && hipMemsetAsync(temp, 0, sizeof(uint32_t), stream) == hipSuccess) {
@@ -331,14 +329,14 @@ static inline nvcompStatus_t decompress_async(
     hipLaunchKernelGGL(Team16, dim3((unsigned)batch_size), dim3(1024), 0, stream, one_each);
   } else if (batch_size <= kTeamMaxBatch) {
     /* small batches cannot fill the card with one wave per chunk: a workgroup per chunk (common/lz_team.hip.h) */
-    launch_persistent<Team8>(stream, temp, temp_bytes, batch_size, 1, 512, 0, true,
+    launch_persistent<Team8>(stream, temp, temp_bytes, batch_size, 1, 512, 0,
                              [&](uint32_t* ticket, size_t first_dynamic) { return Launch{b, ticket, first_dynamic, nullptr}; });
   } else if (batch_size <= kPairMaxBatch) {
     /* (round 2's path for small batches: two waves per chunk, producer / consumer) */
     hipLaunchKernelGGL(Pair, dim3((unsigned)batch_size), dim3(128), 0, stream, b);
   } else {
     launch_persistent<Window>(stream, temp, temp_bytes, batch_size, kDecWaves, 64 * kDecWaves, NVCOMP_LZ_MAX_WG_PER_CU,
-                              NVCOMP_LZ_PERSISTENT != 0, [&](uint32_t* ticket, size_t waves) {
+                              [&](uint32_t* ticket, size_t waves) {
                                 return Launch{b, ticket, waves, with_index ? index_base(temp, temp_bytes, waves) : nullptr};
                               });
   }
@@ -404,7 +402,7 @@ static inline nvcompStatus_t compress_async(const CompressCall& c)
     return nvcompErrorInvalidValue;
   }
   clear_stale_error();
-  launch_persistent<Kernel>(c.stream, c.temp, c.temp_bytes, c.batch_size, WAVES, 64 * WAVES, 0, NVCOMP_LZ_PERSISTENT != 0,
+  launch_persistent<Kernel>(c.stream, c.temp, c.temp_bytes, c.batch_size, WAVES, 64 * WAVES, 0,
                             [&](uint32_t* ticket, size_t first_dynamic) {
                               return CompressLaunch{c.in_ptrs, c.in_bytes, c.max_chunk_bytes, c.batch_size,
                                                     c.out_ptrs, c.out_bytes, ticket, first_dynamic};

@@ -5,7 +5,7 @@
  * WHY. Measured in round 6 (scripts/microbench/valu_issue.hip, profiles/r06_valu_issue_*.jsonl): a wave64 vector
  * instruction of the decoders' mix holds its SIMD for 4 cycles, the window decoder is at 0.93-0.95 of vector issue, and
  * folding its far-match loads onto resident lines moves it by 4 % (profiles/r06_far_ablate.jsonl): the only lever is the
- * instruction count. The token chase of common/lz_window.hip.h (chase_build + chase_tokens) is 30 % of a wave's time: it
+ * instruction count. The token chase of common/lz_chase.hip.h (chase_build + chase_tokens) is 30 % of a wave's time: it
  * computes "the distance to the next token" for EVERY stream position -- 256 positions for the ~54 tokens among them --
  * and builds five jump tables over them.
  *
@@ -190,7 +190,6 @@ __device__ __forceinline__ Index build(const uint8_t* in, uint32_t in_len, uint8
   {
     const uint32_t back = s_lo > kRunIn ? s_lo - kRunIn : 0u;
     const uint32_t start = back > first ? back : first; /* lanes whose run-in reaches the chunk's start walk the true chain */
-#ifndef NVCOMP_LZX_NO_TOUCH
     /* every lane's stretch of the stream is asked for at once (a load per 128-byte line, the data is not looked at): the
      * phases of the walk then wait for the L2, not for HBM -- one long round trip per chunk instead of one per phase
      * (the decoder with an index was 26 % fewer vector instructions and 21 % MORE time: waiting, gpurun r6pmc) */
@@ -201,7 +200,6 @@ __device__ __forceinline__ Index build(const uint8_t* in, uint32_t in_len, uint8
       }
       wave::touch(acc);
     }
-#endif
     walk<Format>(in, in_len, blk, true, start, s_lo, s_hi, list, entry, n, exit_pos, stopped);
   }
   /* ---- join: a lane's entry must be its predecessor's exit ---- */

@@ -31,12 +31,9 @@
 #ifndef NVCOMP_LZ_PAIR_MAX_BATCH
 #define NVCOMP_LZ_PAIR_MAX_BATCH 4096 /* two waves per chunk up to here: 319 against 310 GB/s at 4 096 chunks since the pair kernels lost their scratch
                                         * (round 4, profiles/r04_final_nsweep.jsonl; 3 072 before); 412 against 454 at 8 192. Round 6: the kernels hold
-                                        * the one-wave loop with the run executor for the chunks that shrank 8 x (NVCOMP_LZ_PAIR_SOLO), whose
+                                        * the one-wave loop with the run executor for the chunks that shrank 8 x (lzl::decode_pair: `solo`), whose
                                         * registers cost them the eighth wave per SIMD -- 7 168 resident waves for 8 192 at 4 096 chunks -- and the
                                         * mix at 4 096 chunks is FASTER so: 328 against 317 GB/s (and 301 in the persistent kernel; gpurun r6ak) */
-#endif
-#ifndef NVCOMP_LZ_PAIR_SOLO
-#define NVCOMP_LZ_PAIR_SOLO 1 /* A/B: 0 = every chunk of the two-wave kernels by producer and consumer */
 #endif
 #ifndef NVCOMP_LZ_TEAM_MAX_BATCH
 #define NVCOMP_LZ_TEAM_MAX_BATCH 512 /* a WORKGROUP per chunk up to this many chunks (common/lz_team.hip.h): 263 us per chunk against 467 (two waves) and 677 (one); from 1 024 chunks on two waves per chunk keep more chunks in flight (profiles/r04_team.jsonl) */
@@ -50,9 +47,6 @@
                                    * spilling, and run SLOWER there than at 7 (LZ4 mix 632 vs 644 GB/s, sorted-key column 686 vs
                                    * 750): 28 waves per CU already keep the vector, scalar and LDS pipes two thirds busy, four more
                                    * only add contention for L1 / L2 and the LDS pipe; 6 is worse again (607). */
-#endif
-#ifndef NVCOMP_LZ_PERSISTENT
-#define NVCOMP_LZ_PERSISTENT 1 /* A/B: 0 = one wave per chunk, static mapping (round 2) */
 #endif
 
 namespace lzl {

@@ -37,74 +37,45 @@
 
 namespace lzm {
 
-#ifndef NVCOMP_LZM_HASH_BITS
-#define NVCOMP_LZM_HASH_BITS 12
-#endif
-/* One-byte tags beside the positions (A/B build): a probe would look at the candidate's bytes in memory only when eight
- * more hash bits agree. Measured (profiles/archive/r02_lz_compress.json): no gain -- the compressor is bound by the LENGTH of its
- * dependent chain per window, not by the candidate fetches -- and the extra 4 KiB of LDS per wave cost occupancy. Off. */
-/* The position side of a window (the 40 bytes around each of its 64 positions) comes out of a per-wave LDS image of the
- * input, filled 512 bytes at a time by ONE coalesced load per lane, instead of four byte-strided lane loads per window:
- * those cost the L1 (TCP) one tag lookup per lane and instruction -- 10.3 G lookups per GiB, one per cycle and CU for
- * the whole kernel (profiles/archive/r02_lz_compress.json, counters). 0 = the round-2 register path (A/B build). */
-#ifndef NVCOMP_LZM_STAGE
-#define NVCOMP_LZM_STAGE 1
-#endif
+/* What was tried here and is no longer in the code ("retired switches", names the commit that still has it):
+ *  - One-byte tags beside the positions: a probe would look at the candidate's bytes in memory only when eight more hash
+ *    bits agree. Measured (profiles/archive/r02_lz_compress.json): no gain -- the compressor is bound by the LENGTH of
+ *    its dependent chain per window, not by the candidate fetches -- and the extra 4 KiB of LDS per wave cost occupancy.
+ *  - Inserting only the positions that no selected match covers (1.7841 -> 1.7976 greedy, 1.8392 -> 1.8430 lazy at 3 456
+ *    entries; worse than inserting everything once the table has 8 192): every position is inserted.
+ *  - The round-2 register path, four byte-strided lane loads per window in place of the input image below: those cost
+ *    the L1 (TCP) one tag lookup per lane and instruction -- 10.3 G lookups per GiB, one per cycle and CU for the whole
+ *    kernel (profiles/archive/r02_lz_compress.json, counters).
+ * The selection walk takes one step of lazy evaluation. Measured on the mix with the emulator (8 chunks per class,
+ * weighted by the mix's shares; liblz4 LZ4_compress_default on the same chunks: 1.8455): greedy 1.7841, lazy 1.8392 at
+ * 3 456 table entries; 1.7998 -> 1.8601 at 4 096; 1.8408 -> 1.9165 at 8 192. Two or four steps add 0.0007; asking for a
+ * margin of one byte loses 0.005. */
 /* ---- the output staging (NVCOMP_LZM_STAGE_OUT, A/B build) ----
  * The sequences of a window composed in LDS and written with ONE coalesced store of consecutive dwords (up to three bytes
  * wait for the next window) instead of five or six scattered store instructions. Built and measured in round 3
  * (profiles/archive/r03_compress_ab.jsonl): 115.9 against 117.9 GB/s on the mix, 111.3 against 113.7 for Snappy -- the scattered
  * stores of ten lanes are not what the address unit is busy with (the candidate loads of 64 lanes are), and the 256 bytes
- * come out of the hash table. Off. */
+ * come out of the hash table. Off. (The switch outlived the others of this file: without the flush of the staged bytes --
+ * which does nothing when it is off -- the compiler allocates the registers of lz4_compress_kernel<2> and <4> differently.) */
 #ifndef NVCOMP_LZM_STAGE_OUT
 #define NVCOMP_LZM_STAGE_OUT 0
-#endif
-#ifndef NVCOMP_LZM_TAGS
-#define NVCOMP_LZM_TAGS 0
-#endif
-/* Literal runs of more than 8 bytes come out of the input image instead of memory (emit_small below). */
-#ifndef NVCOMP_LZM_LIT_IMAGE
-#define NVCOMP_LZM_LIT_IMAGE 1
-#endif
-/* One step of lazy evaluation in the selection walk. Measured on the mix with the emulator (8 chunks per class, weighted
- * by the mix's shares; liblz4 LZ4_compress_default on the same chunks: 1.8455): greedy 1.7841, lazy 1.8392 at 3 456
- * table entries; 1.7998 -> 1.8601 at 4 096; 1.8408 -> 1.9165 at 8 192. Two or four steps add 0.0007; asking for a
- * margin of one byte loses 0.005. */
-#ifndef NVCOMP_LZM_LAZY
-#define NVCOMP_LZM_LAZY 1
-#endif
-/* Positions inside a selected match are not inserted into the table (A/B: 1.7841 -> 1.7976 greedy, 1.8392 -> 1.8430
- * lazy at 3 456 entries; worse than inserting everything once the table has 8 192). */
-#ifndef NVCOMP_LZM_INSERT_UNCOVERED
-#define NVCOMP_LZM_INSERT_UNCOVERED 0
 #endif
 #ifndef NVCOMP_LZM_WAVES_PER_SIMD
 #define NVCOMP_LZM_WAVES_PER_SIMD 5 /* what the 8 KiB hash table per wave allows (4-wave workgroups, 160 KB LDS per CU) */
 #endif
-constexpr uint32_t kHashBits = NVCOMP_LZM_HASH_BITS;
 /* Entries of the per-wave table (any multiple of 128). With the input image beside it a wave has 8 KiB of LDS at
  * 5 waves/SIMD (4-wave workgroups, 160 KB per CU): 3456 two-byte entries + 1072 bytes of image (3328 when the A/B output
  * staging takes 256 bytes). */
-#ifdef NVCOMP_LZM_HASH_ENTRIES
-constexpr uint32_t kHashSize = NVCOMP_LZM_HASH_ENTRIES;
-#elif NVCOMP_LZM_STAGE
 constexpr uint32_t kHashSize = NVCOMP_LZM_STAGE_OUT ? 3328 : 3456;
-#else
-constexpr uint32_t kHashSize = 1u << kHashBits;
-#endif
 static_assert(kHashSize % 128 == 0 && kHashSize <= 65536, "the table is cleared 64 dwords at a time");
-/* The table a wave owns, in uint16 units: kHashSize positions (mod 65536), followed by kHashSize one-byte tags in the
- * NVCOMP_LZM_TAGS build. */
-constexpr uint32_t kTableU16 = kHashSize + (NVCOMP_LZM_TAGS ? kHashSize / 2 : 0);
+/* The table a wave owns, in uint16 units: kHashSize positions (mod 65536). */
+constexpr uint32_t kTableU16 = kHashSize;
 constexpr uint32_t kMinMatch = 4;
 /* The candidate side comes with TWO 16-byte loads per lane (8 bytes before the candidate and 24 from it on) instead of
  * three (32 from it on): a lane's load is a lookup of its own in the CU's address unit whatever its width, and the
  * candidate loads were 40 % of a window's lookups in a kernel that is bound by exactly that unit. The per-lane
  * measurement then stops at 24 bytes; longer matches are finished by the whole wave, as before. */
-#ifndef NVCOMP_LZM_CAND32
-#define NVCOMP_LZM_CAND32 1
-#endif
-constexpr uint32_t kLaneCap = NVCOMP_LZM_CAND32 ? 24 : 32; /* per-lane match measurement, compared in registers */
+constexpr uint32_t kLaneCap = 24; /* per-lane match measurement, compared in registers */
 /* Hit lanes in a window from which its first match is probed cooperatively. Runs and periodic columns hit in (nearly)
  * every lane; text hits in about half of them, and at 32 the probe ran on 40 % of its windows to find nothing
  * (60 against 32: +4 % on the mix, +8 % on the int32 column, same ratio). */
@@ -156,22 +127,7 @@ struct ProfClock
 __device__ __forceinline__ uint32_t hash4(uint32_t v)
 {
   const uint32_t h = v * 2654435761u;
-  if constexpr ((kHashSize & (kHashSize - 1)) == 0) {
-    return h >> (32 - kHashBits);
-  } else {
-    return __umulhi(h, kHashSize); /* multiply-shift range reduction onto [0, kHashSize) */
-  }
-}
-
-/* Eight hash bits that do not take part in the index. */
-__device__ __forceinline__ uint32_t tag4(uint32_t v)
-{
-  const uint32_t h = v * 2654435761u;
-  if constexpr ((kHashSize & (kHashSize - 1)) == 0) {
-    return (h >> (24 - kHashBits)) & 0xffu;
-  } else {
-    return (h >> 6) & 0xffu;
-  }
+  return __umulhi(h, kHashSize); /* multiply-shift range reduction onto [0, kHashSize) */
 }
 
 /* Wave-cooperative extension of a match known to be at least `have` bytes long: 64 bytes per step, compared as 16
@@ -215,29 +171,16 @@ struct Around
   uint32_t fwd[8];
 };
 
-/* Both loads are unaligned 16-byte lane loads of consecutive addresses one byte apart: a wave touches two or three
- * cache lines. `with_pre` = pos >= 8. The caller guarantees pos + 32 <= the end of the chunk. */
-__device__ __forceinline__ void load_around(Around& r, const uint8_t* __restrict__ src, uint32_t pos, bool with_pre)
-{
-  const wave::u32x4 a = wave::gload_u32x4(src + pos);
-  const wave::u32x4 b = wave::gload_u32x4(src + pos + 16);
-  r.fwd[0] = a.x, r.fwd[1] = a.y, r.fwd[2] = a.z, r.fwd[3] = a.w;
-  r.fwd[4] = b.x, r.fwd[5] = b.y, r.fwd[6] = b.z, r.fwd[7] = b.w;
-  r.pre[0] = 0, r.pre[1] = 0;
-  if (with_pre) {
-    r.pre[0] = wave::gload_u32(src + pos - 8);
-    r.pre[1] = wave::gload_u32(src + pos - 4);
-  }
-}
-
-/* ---- the input image (NVCOMP_LZM_STAGE) ----
+/* ---- the input image ----
+ * The position side of a window (the 40 bytes around each of its 64 positions) comes out of a per-wave LDS image of the
+ * input, filled 512 bytes at a time by ONE coalesced load per lane.
  * Two 512-byte blocks of the chunk, block b (bytes [512 b, 512 b + 512)) in slot b & 1, so that byte p lives at image
  * offset p & 1023; the first kStageMirror bytes of slot 0 are repeated behind slot 1, which lets a lane read its 44
  * bytes from ascending addresses whichever way round the two blocks lie. A window needs at most two consecutive
  * blocks. Lane l carries bytes [8 l, 8 l + 8) of a block. */
 constexpr uint32_t kStageBlock = 512;
 constexpr uint32_t kStageMirror = 48;
-constexpr uint32_t kStageBytes = NVCOMP_LZM_STAGE ? 2 * kStageBlock + kStageMirror : 8;
+constexpr uint32_t kStageBytes = 2 * kStageBlock + kStageMirror;
 constexpr uint32_t kNoBlock = ~0u;
 constexpr uint32_t kOutStage = NVCOMP_LZM_STAGE_OUT ? 256 : 0;
 constexpr uint32_t kImageBytes = kStageBytes + kOutStage; /* what a wave's `image` argument points at */
@@ -258,7 +201,7 @@ __device__ __forceinline__ void stage_commit(uint8_t* image, uint32_t blk, uint6
   }
 }
 
-/* load_around() out of the image: eleven aligned dwords, realigned by the position's low two bits. */
+/* The bytes around a position out of the image: eleven aligned dwords, realigned by the position's low two bits. */
 __device__ __forceinline__ void stage_around(Around& r, const uint8_t* image, uint32_t pos)
 {
   const uint32_t from = (pos - 8u) & (2 * kStageBlock - 1);
@@ -337,9 +280,6 @@ __device__ __forceinline__ Probe probe_fast(
   {
     const uint32_t slot = hash4(p.word);
     p.cand = table_candidate(pos, table[slot], ok, reach);
-#if NVCOMP_LZM_TAGS
-    ok = ok && ((const uint8_t*)(table + kHashSize))[slot] == tag4(p.word);
-#endif
   }
   const uint32_t near = neighbour_repeat(p.word, eligible, stride);
   if (near) {
@@ -354,17 +294,12 @@ __device__ __forceinline__ Probe probe_fast(
   }
   c.pre[0] = 0, c.pre[1] = 0;
   if (ok) {
-#if NVCOMP_LZM_STAGE
     /* 40 bytes from 8 before the candidate in three loads (a candidate in the first 8 bytes of the chunk: 40 from it) */
     const bool cback = p.cand >= kBackMax;
     const uint8_t* cp = src + p.cand - (cback ? kBackMax : 0u);
     const wave::u32x4 a = wave::gload_u32x4(cp);
     const wave::u32x4 b = wave::gload_u32x4(cp + 16);
-#if NVCOMP_LZM_CAND32
     const uint64_t d = ~(((uint64_t)me.fwd[7] << 32) | me.fwd[6]); /* not fetched: bytes 24..31 compare unequal */
-#else
-    const uint64_t d = wave::gload_u64(cp + 32);
-#endif
     c.pre[0] = cback ? a.x : 0u;
     c.pre[1] = cback ? a.y : 0u;
     c.fwd[0] = cback ? a.z : a.x;
@@ -375,9 +310,6 @@ __device__ __forceinline__ Probe probe_fast(
     c.fwd[5] = cback ? b.w : b.y;
     c.fwd[6] = cback ? (uint32_t)d : b.z;
     c.fwd[7] = cback ? (uint32_t)(d >> 32) : b.w;
-#else
-    load_around(c, src, p.cand, p.cand >= kBackMax);
-#endif
   }
   uint32_t x[8];
 #pragma unroll
@@ -420,9 +352,6 @@ __device__ __forceinline__ Probe probe_safe(
     p.word = lz::ld_u32(src + pos);
     const uint32_t slot = hash4(p.word);
     p.cand = table_candidate(pos, table[slot], ok, reach);
-#if NVCOMP_LZM_TAGS
-    ok = ok && ((const uint8_t*)(table + kHashSize))[slot] == tag4(p.word);
-#endif
   }
   const uint32_t near = neighbour_repeat(p.word, eligible, stride);
   if (near) {
@@ -490,30 +419,19 @@ __device__ __forceinline__ uint32_t encode_chunk(
     uint32_t ip = 0;
     constexpr uint32_t kWin = 64 * STRIDE; /* bytes a window covers */
     uint32_t skip = 0;        /* leading BYTES of the window that the previous step's last match already covers */
-#if NVCOMP_LZM_STAGE
     uint32_t have0 = kNoBlock, have1 = kNoBlock; /* the blocks in the image's two slots */
     uint32_t coming = kNoBlock;                  /* the block requested ahead, in `piece` until its slot is free */
     uint64_t piece = 0;
-#else
-    Around ahead;             /* position side of window `ahead_ip`, requested one step early */
-    uint32_t ahead_ip = ~0u;
-#pragma unroll
-    for (uint32_t i = 0; i < 8; ++i) {
-      ahead.fwd[i] = 0;
-    }
-    ahead.pre[0] = 0, ahead.pre[1] = 0;
-#endif
     while (ip <= last_start) {
       const uint32_t pos = ip + lane * STRIDE;
       const bool eligible = pos <= last_start;
       /* wave-uniform: every lane may read its 32 bytes (and the 8-byte pieces holding them lie inside the chunk) */
-      const bool fast = ip + 63 * STRIDE + 32 + (NVCOMP_LZM_STAGE ? 7 : 0) <= n;
+      const bool fast = ip + 63 * STRIDE + 32 + 7 <= n;
       LZM_T(0); /* loop top */
       Probe pr;
       Around me; /* fast windows: the bytes around this lane's position stay in registers until its literals are written */
       me.pre[0] = 0, me.pre[1] = 0;
       if (fast) {
-#if NVCOMP_LZM_STAGE
         const uint32_t first = (ip >= 8 ? ip - 8 : 0u) / kStageBlock;
         const uint32_t last = (ip + 63 * STRIDE + 31) / kStageBlock; /* first or first + 1 */
         if (coming != kNoBlock) {
@@ -544,17 +462,6 @@ __device__ __forceinline__ uint32_t encode_chunk(
             coming = next;
           }
         }
-#else
-        if (ahead_ip == ip) {
-          me = ahead;
-        } else {
-          load_around(me, src, pos, pos >= kBackMax);
-        }
-        if (ip + kWin + 63 * STRIDE + 32 <= n) { /* the next window's position side travels while this one is worked on */
-          ahead_ip = ip + kWin;
-          load_around(ahead, src, pos + kWin, true);
-        }
-#endif
         pr = probe_fast(src, table, me, pos, eligible, match_end, STRIDE, Emitter::kReach);
       } else {
         pr = probe_safe(src, table, pos, eligible, match_end, STRIDE, Emitter::kReach);
@@ -570,21 +477,13 @@ __device__ __forceinline__ uint32_t encode_chunk(
         if (mine) {
           const uint32_t slot = hash4(word);
           table[slot] = (uint16_t)pos;
-#if NVCOMP_LZM_TAGS
-          ((uint8_t*)(table + kHashSize))[slot] = (uint8_t)tag4(word);
-#endif
         }
         wave::sync();
       };
-#if !NVCOMP_LZM_INSERT_UNCOVERED
       insert_lanes(eligible);
-#endif
       const uint64_t hits = wave::ballot(pr.found && lane * STRIDE >= skip);
       LZM_T(2); /* table insert */
       if (hits == 0) {
-#if NVCOMP_LZM_INSERT_UNCOVERED
-        insert_lanes(eligible && lane * STRIDE >= skip);
-#endif
         /* no match starts in this window: its positions become literals */
         skip = skip > kWin ? skip - kWin : 0;
         ip += kWin;
@@ -603,9 +502,6 @@ __device__ __forceinline__ uint32_t encode_chunk(
         const uint64_t diff = ~wave::ballot(same);
         uint32_t len0 = diff ? kMinMatch + wave::ctz64(diff) : extend_match(src, mpos, mcand, kMinMatch + 64, match_end);
         if (len0 >= kLaneCap) {
-#if NVCOMP_LZM_INSERT_UNCOVERED
-          insert_lanes(eligible && lane <= f0 && lane * STRIDE >= skip);
-#endif
           /* grow it backwards over the pending literals (what the CPU compressors call catching up): lane l
            * compares the l-th byte before the match with the l-th byte before its source */
           {
@@ -639,15 +535,11 @@ __device__ __forceinline__ uint32_t encode_chunk(
        * find the next hit, read its length, mask off what the match covers. Where each selected lane's literal run
        * starts (the end of the match selected before it) is worked out afterwards, for all of them at once. */
       uint64_t selected = 0;
-#if NVCOMP_LZM_INSERT_UNCOVERED
-      uint64_t covered = 0;
-#endif
       uint32_t cur = 0;       /* window-relative BYTE position the next match may start at */
       uint64_t rest = hits;
       while (rest) {
         uint32_t f = wave::ctz64(rest);
         uint32_t flen = wave::read_lane(mlen, f);
-#if NVCOMP_LZM_LAZY
         /* one step of lazy evaluation: every lane has measured its own match, so "does the next position start a
          * longer one?" is one more lane read. The shorter match becomes a literal. */
         if (f < 63 && ((hits >> (f + 1)) & 1) && flen < kLaneCap) {
@@ -657,7 +549,6 @@ __device__ __forceinline__ uint32_t encode_chunk(
             flen = l1;
           }
         }
-#endif
         selected |= 1ull << f;
         cur = f * STRIDE + flen;
         if (flen >= kLaneCap) { /* the capped match may be much longer: measure it with the whole wave */
@@ -668,14 +559,8 @@ __device__ __forceinline__ uint32_t encode_chunk(
         {
           const uint32_t next_lane = (cur + STRIDE - 1) / STRIDE; /* first lane at or behind the match's end */
           rest = next_lane < 64 ? (hits & (~0ull << next_lane)) : 0ull;
-#if NVCOMP_LZM_INSERT_UNCOVERED
-          covered |= (next_lane < 64 ? ~(~0ull << next_lane) : ~0ull) & (f < 63 ? (~0ull << (f + 1)) : 0ull);
-#endif
         }
       }
-#if NVCOMP_LZM_INSERT_UNCOVERED
-      insert_lanes(eligible && lane * STRIDE >= skip && !((covered >> lane) & 1));
-#endif
       const uint32_t lit_from = ip + cur; /* behind the last selected match */
       /* a selected lane's run starts where the selected match below it ends (the first one's: at the anchor) */
       uint32_t prev_end;
@@ -739,16 +624,12 @@ __device__ __forceinline__ uint32_t encode_chunk(
           }
           const bool from_mem = small && !from_regs && lit_len != 0;
           const uint8_t* ls = src + prev_end;
-#if NVCOMP_LZM_STAGE && NVCOMP_LZM_LIT_IMAGE
           /* A run of more than 8 bytes is read back -- out of the input image when both its ends lie in the two blocks
            * the image holds (nearly always: a run of up to 64 bytes that ends inside this window): six windows in ten
            * have such a run, and read from memory each cost its window a dependent round trip (the phase clock put
            * 17 % of the compressor's time into this copy). */
           const uint32_t blk_a = prev_end / kStageBlock, blk_b = (prev_end + lit_len - 1) / kStageBlock;
           const bool in_image = fast && (blk_a & 1u ? have1 : have0) == blk_a && (blk_b & 1u ? have1 : have0) == blk_b;
-#else
-          const bool in_image = false;
-#endif
           const bool lit4 = from_mem && lit_len >= 4;
           for (uint32_t base4 = 0; wave::ballot(lit4 && lit_len > base4) != 0; base4 += 16) {
             if (lit4 && lit_len > base4) {

@@ -8,7 +8,7 @@
  * every lane compares its 16 bytes with the 16 bytes p back (two loads, a funnel shift, a zero-byte mask), and only
  * the MISMATCHES -- two or three a KiB -- cost scalar work: a mismatch ends the stretch of equal bytes in front of it,
  * and a stretch of four bytes or more is a match of offset p (the same sequences liblz4's HC parser finds on these
- * columns; the decoder's run executor, common/lz_window.hip.h, takes them 60 at a time).
+ * columns; the decoder's run executor, common/lz_run_batch.hip.h, takes them 60 at a time).
  *
  * Used for a chunk whose first KiB is such a copy to 15 parts in 16; given up (the caller's match finder starts over)
  * when the output grows beyond a quarter of the input consumed. Format-independent: sequences go out through the

@@ -38,9 +38,6 @@ namespace wide {
  * is looked at -- a match found up to three positions late gets those bytes back by its growth backwards -- until a step
  * has a hit again; 0 = never. Every position still goes into the table. Why: a candidate look is one scattered 12-byte
  * load, and on noise every position has a (colliding) candidate: 1 GiB of noise asks the fabric for 10^9 lines. */
-#ifndef NVCOMP_LZMW_FIRST_BATCH_EARLY
-#define NVCOMP_LZMW_FIRST_BATCH_EARLY 1
-#endif
 #ifndef NVCOMP_LZMW_QUIET_STEPS
 #define NVCOMP_LZMW_QUIET_STEPS 2
 #endif
@@ -493,7 +490,6 @@ __device__ __forceinline__ uint32_t encode_chunk(
         total_long = base;
         wave::sync_wave();
       }
-#if NVCOMP_LZMW_FIRST_BATCH_EARLY
       /* (the lengths known so far wait in LDS, beside the ones the measurements will write: four registers less across the
        * probe, whose spills would be reloaded -- and waited for, with everything else in flight -- on the way) */
 #pragma unroll
@@ -512,14 +508,12 @@ __device__ __forceinline__ uint32_t encode_chunk(
         const uint32_t p = act ? ip + (e & 255u) : ip + 8;
         first_bytes = measure_request(src, n, p, p - (e >> 8), act).b;
       }
-#endif
       LZM_T(4);
 
       /* ---- the NEXT step's probe and word-check loads: they travel while this step is measured, selected and written.
        * (The step behind a long match starts elsewhere: then this probe only put positions inside that match into the
        * table.) `pr` is free: what this step needs of it are the candidates and the hit masks ---- */
       const uint32_t nip = ip + kStep;
-#if NVCOMP_LZMW_FIRST_BATCH_EARLY
       const auto finish_first = [&]() {
         if (total_long != 0) {
           const bool act = lane < total_long;
@@ -542,15 +536,6 @@ __device__ __forceinline__ uint32_t encode_chunk(
         finish_first();
       }
       for (uint32_t b0 = 64; b0 < total_long; b0 += 128) {
-#else
-      if (nip <= last_start) {
-        probe_step<Emitter>(pr, im, src, n, table, nip, last_start, last_start);
-      }
-      LZM_T(1);
-
-      /* two batches a round: their loads travel together */
-      for (uint32_t b0 = 0; b0 < total_long; b0 += 128) {
-#endif
         const bool act0 = b0 + lane < total_long, act1 = b0 + 64 + lane < total_long;
         const uint32_t e0 = act0 ? queue[b0 + lane] : 8u << 8;
         const uint32_t e1 = act1 ? queue[b0 + 64 + lane] : 8u << 8;
@@ -574,13 +559,7 @@ __device__ __forceinline__ uint32_t encode_chunk(
       uint64_t capped[kSub];
 #pragma unroll
       for (uint32_t k = 0; k < kSub; ++k) {
-#if NVCOMP_LZMW_FIRST_BATCH_EARLY
         mlen[k] = results[64 * k + lane];
-#else
-        if (longer[k]) {
-          mlen[k] = results[64 * k + lane];
-        }
-#endif
         hits[k] = wave::ballot(mlen[k] != 0);
         capped[k] = wave::ballot(mlen[k] >= kCap);
       }
@@ -589,7 +568,6 @@ __device__ __forceinline__ uint32_t encode_chunk(
       /* ---- select ---- */
       /* lazy evaluation, per lane: a match shorter than the one starting at the next position is passed over (the next
        * position's is looked at in its turn) */
-#if NVCOMP_LZM_LAZY
 #pragma unroll
       for (uint32_t k = 0; k < kSub; ++k) {
         uint32_t ahead = wave::next_lane(mlen[k]);
@@ -599,7 +577,6 @@ __device__ __forceinline__ uint32_t encode_chunk(
         }
         hits[k] = wave::ballot(mlen[k] != 0 && !(mlen[k] < kCap && ahead > mlen[k]));
       }
-#endif
       uint32_t cur = skip;
       uint64_t sel[kSub];
 #pragma unroll

@@ -25,6 +25,8 @@
 #pragma once
 
 #include "common/lz_window.hip.h"
+#include "common/lz_chase.hip.h"
+#include "common/lz_run_batch.hip.h"
 
 namespace lzw {
 namespace pair {
@@ -150,7 +152,7 @@ __device__ __forceinline__ void produce(const uint8_t* __restrict__ in, uint32_t
   }
 }
 
-/* RUNS: the rounds try the run executor first (LZ4's A/B build NVCOMP_LZ4_PAIR_RUNS). */
+/* RUNS: the rounds try the run executor first (Format::kPairRuns; false in both formats: their chunks of runs go to Format::alone). */
 template <class FrontEnd, bool CHECKED, bool RUNS>
 __device__ __forceinline__ uint32_t consume(
     const uint8_t* __restrict__ in, uint32_t in_len, uint8_t* out, uint32_t out_cap, uint8_t* lds, uint32_t& err)

@@ -37,6 +37,7 @@
 #endif
 
 #include "common/lz_window.hip.h"
+#include "common/lz_chase.hip.h"
 #include "common/lz_pair.hip.h"
 
 namespace lzt {

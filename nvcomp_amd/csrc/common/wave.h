@@ -333,7 +333,7 @@ __device__ __forceinline__ uint32_t scan_max_inclusive(uint32_t v)
  * of the highest lane j <= k whose mask has that bit set, and with the OR of the masks of lanes 0 .. k. Value bits are
  * kept zero where the mask is zero. Same DPP ladder as the sums (the operator is associative, not commutative: a lane
  * combines what it receives from below with its own). The run executor of the LZ decoders carries the 16-byte pattern
- * of a run from sequence to sequence with it (common/lz_window.hip.h: execute_run_batch). */
+ * of a run from sequence to sequence with it (common/lz_run_batch.hip.h: execute_run_batch). */
 __device__ __forceinline__ void scan_last_writer(uint32_t& val, uint32_t& mask)
 {
   val &= mask;

@@ -11,7 +11,7 @@
  *              literal ring in LDS. A symbol's length is only known once it is decoded, so the wave decodes
  *              SPECULATIVELY at every bit position of a 256-bit window (four per lane: one lookup for the
  *              literal/length code, one for the distance code), turns the lengths into jump tables by pointer
- *              doubling (the token chase of common/lz_window.hip.h, on bit positions) and reads the true chain of
+ *              doubling (the token chase of common/lz_chase.hip.h, on bit positions) and reads the true chain of
  *              symbol starts off them, 32 at a time; lane k then decodes symbol k for good and the records are
  *              assembled with ballots. What the lookups cannot tell (a code longer than the lookup, end of block,
  *              an illegal symbol) is left to a wave-uniform decoder that takes one symbol at a time (the scalar
@@ -491,7 +491,7 @@ struct Scan
 };
 
 /* Tables of the window that starts at bit position q: J_i[p] = bits from p to the 2^i-th symbol after it (255 = it
- * leaves the window, a symbol on the way cannot be told, or the sum does not fit a byte). lz_window.hip.h: chase_build,
+ * leaves the window, a symbol on the way cannot be told, or the sum does not fit a byte). lz_chase.hip.h: chase_build,
  * on bit positions. */
 __device__ __forceinline__ void scan_build(Scan& c, const lzw::InRing& ir, const Code& ll, const Code& dd, uint32_t q)
 {
@@ -590,7 +590,7 @@ __device__ __forceinline__ uint32_t scan_round(
       LZ_STAT("deflate_builds", 1);
       LZW_T(1);
     }
-    /* Lane n: the n-th symbol from q, if the chain gets there inside this window. Lane arithmetic only (lz_window.hip.h:
+    /* Lane n: the n-th symbol from q, if the chain gets there inside this window. Lane arithmetic only (lz_chase.hip.h:
      * chase_tokens): a lane follows the levels named by the bits of n; a level it does not take adds 0; 255 poisons the
      * lane through `worst`; the position wraps inside the table. Ranks 32 and up start at the 32nd symbol, two steps of the
      * 16-symbol table from the start (every lane reads the same two bytes). */

@@ -13,6 +13,8 @@
 #pragma once
 
 #include "common/lz_window.hip.h"
+#include "common/lz_chase.hip.h"
+#include "common/lz_run_batch.hip.h"
 #include "common/lz_index.hip.h"
 
 #include <type_traits>
@@ -297,7 +299,7 @@ __device__ __forceinline__ void parse_batch(const R& r, uint32_t p, uint32_t fro
   s.match_off = mine ? ((uint32_t)x & 0xffffu) : 0;
   s.match_len = mine ? mcode + 4 + (mcode == 15 ? mext : 0u) : 0;
   bad = false;
-  /* (a mask of single compares joined on the scalar unit: common/lz_window.hip.h, steps_for) */
+  /* (a mask of single compares joined on the scalar unit: common/lz_copy.hip.h, steps_for) */
   const uint64_t rest = wave::ballot(lane - from < to - from)
                         & (wave::ballot(lit2) | wave::ballot(n255 >= 6) | wave::ballot(p < r.lo) | wave::ballot(q + 8 >= lim));
   if (rest) {
@@ -385,8 +387,6 @@ struct NoIndex
 };
 
 /* Decode one chunk with the calling wave; `lds` is this wave's kLdsPerWave bytes. */
-/* ABLATE (profiling builds only, results are wrong by construction): 1 = stop after the
- * token chase, 2 = after the parse, 0 = the real decoder. */
 /* RUNS: the loop tries lzw::execute_run_batch (sorted keys, typed columns). Its mere presence in the loop costs every
  * other kind of data 1.5-2 % (block placement and register allocation of the batch executor around it: gpurun r6u, r6v --
  * the same with the attempts gated off at run time), so the kernels instantiate the loop twice and pick per chunk by what
@@ -395,7 +395,7 @@ struct NoIndex
  * the instantiation, not of the call: with `index_scratch` tested at run time the loop of every build kept the index's
  * reader, its branches and the three registers settle() holds across the far-match wait (928 of 5 591 vector instructions
  * of the kernel, 12 of 18 SGPR spills). false: no Index object exists and index_scratch is not looked at. */
-template <bool CHECKED, int ABLATE = 0, bool RUNS = false, bool INDEXED = false>
+template <bool CHECKED, bool RUNS = false, bool INDEXED = false>
 __device__ __forceinline__ uint32_t decode_chunk(
     const uint8_t* __restrict__ in, uint32_t in_len, uint8_t* out, uint32_t out_cap, uint8_t* lds, uint32_t& err,
     uint8_t* index_scratch = nullptr)
@@ -416,9 +416,6 @@ __device__ __forceinline__ uint32_t decode_chunk(
   if constexpr (INDEXED) {
     ix = lzx::build<IndexFormat>(in, in_len, lds, index_scratch);
     LZW_T(15); /* the token index */
-#ifdef NVCOMP_LZX_BUILD_ONLY /* profiling builds only: the index is built and thrown away (what the walk costs in place) */
-    ix.lanes = 0, ix.ahead_n = 0, ix.resume = 0;
-#endif
     resume = ix.resume;
   }
   lzw::InRing ir;
@@ -434,11 +431,9 @@ __device__ __forceinline__ uint32_t decode_chunk(
    * sequence) a round executes only a handful of the 64 sequences a chase delivers: chasing again for the rest every
    * round was 5 000 cycles per SEQUENCE on the reference's own published shape (profiles/archive/r02_mortgage_like.json).
    * The chase runs only when fewer than kRefillBelow token positions are left; on text a round takes all 64 and
-   * every round refills, as before. NVCOMP_LZ4W_KEEP_PARSED = 1 also keeps the parsed FIELDS in registers across
-   * rounds (four more live registers); 0 parses the positions in hand again every round (two LDS round trips). */
-#ifndef NVCOMP_LZ4W_KEEP_PARSED
-#define NVCOMP_LZ4W_KEEP_PARSED 1 /* measured: headline 498 vs 500 GB/s (noise), mortgage-like column 545 vs 442 */
-#endif
+   * every round refills, as before. The parsed FIELDS stay in registers across rounds too (four more live registers);
+   * parsing the positions in hand again every round (two LDS round trips) measured 498 against 500 GB/s on the headline
+   * batch (noise) and 442 against 545 on the mortgage-like column. */
   constexpr uint32_t kRefillBelow = 24;
   lzw::RunGate gate = lzw::kRunGateInit;
   lz::Seq s;
@@ -454,7 +449,7 @@ __device__ __forceinline__ uint32_t decode_chunk(
     if (count == 0 && !indexed && c.q >= ir.vend) {
       break;
     }
-    uint32_t before = NVCOMP_LZ4W_KEEP_PARSED ? count : 0u; /* lanes [before, count) are parsed this round */
+    const uint32_t before = count; /* lanes [before, count) are parsed this round */
     const bool refill = count < kRefillBelow && (indexed || c.q < ir.vend);
     if (refill && indexed) {
       if constexpr (INDEXED) {
@@ -475,24 +470,14 @@ __device__ __forceinline__ uint32_t decode_chunk(
       lzw::in_ensure(ir, oldest, (c.q & ~(lzw::kInBlock - 1)) + 3 * lzw::kInBlock);
       LZW_T(0);
       count = lzw::chase_tokens(c, ir, seqpos, count, DeltaFn(), SlowFn());
-      if (ABLATE == 1) {
-        op += wave::reduce_add(lane < count ? seqpos : 0u) & 1u;
-        count = 0;
-        continue;
-      }
     }
-    if (refill || !NVCOMP_LZ4W_KEEP_PARSED) {
+    if (refill) {
       lz::Seq fresh;
       bool bad;
       parse_batch(ir, seqpos, before, count, fresh, bad);
       LZW_T(3);
       if (lane >= before) {
         s = fresh;
-      }
-      if (ABLATE == 2) {
-        op += wave::reduce_add(s.lit_len + s.match_len + s.match_off) & 1u;
-        count = 0;
-        continue;
       }
       if (wave::ballot(bad)) {
         err |= lz::kErrInput;
@@ -514,7 +499,7 @@ __device__ __forceinline__ uint32_t decode_chunk(
           lzx::settle(ix);
         }
       };
-      take = lzw::execute_window_batch<CHECKED, false, decltype(settle), NVCOMP_LZW_LAZY_FLUSH && !RUNS>(ir, ow, out_cap, op, count, s, err, big, settle);
+      take = lzw::execute_window_batch<CHECKED, false, decltype(settle)>(ir, ow, out_cap, op, count, s, err, big, settle);
       if (CHECKED && err) {
         return 0;
       }
@@ -534,9 +519,7 @@ __device__ __forceinline__ uint32_t decode_chunk(
     if (take < count) {
       const uint32_t from = (lane + take) & 63u;
       seqpos = wave::shuffle(seqpos, from);
-#if NVCOMP_LZ4W_KEEP_PARSED
       lzw::drop_front(s, take, count);
-#endif
     }
     count -= take;
   }

@@ -9,6 +9,8 @@
 #pragma once
 
 #include "common/lz_window.hip.h"
+#include "common/lz_chase.hip.h"
+#include "common/lz_run_batch.hip.h"
 #include "snappy/snappy_decode.hip.h"
 
 namespace snappyw {
@@ -229,7 +231,7 @@ __device__ __forceinline__ bool parse_fast(
   const uint64_t c = is_lit ? y : w;
   const uint32_t tag = (uint32_t)c & 0xffu;
   const uint32_t k = tag & 3u;
-  /* (a mask of single compares joined on the scalar unit: common/lz_window.hip.h, steps_for) */
+  /* (a mask of single compares joined on the scalar unit: common/lz_copy.hip.h, steps_for) */
   if (wave::ballot(lane - from < to - from) & wave::ballot((t & 3u) == 0) & wave::ballot(code >= 60)) {
     return false;
   }
@@ -500,7 +502,7 @@ __device__ __forceinline__ uint32_t decode_chunk(
       gate = wave::uniform(lzw::run_gate_tried(gate, take, misfit));
     }
     if (take == 0) {
-      take = lzw::execute_window_batch<CHECKED, false, lzw::NoHook, NVCOMP_LZW_LAZY_FLUSH && !RUNS>(ir, ow, limit, op, count, s, err, big);
+      take = lzw::execute_window_batch<CHECKED, false>(ir, ow, limit, op, count, s, err, big);
       if (CHECKED && err) {
         return 0;
       }

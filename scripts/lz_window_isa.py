@@ -2,6 +2,7 @@
 """Static instruction counts of the persistent LZ window kernels, from the compiler's assembly.
 
 usage: lz_window_isa.py [--format lz4|snappy] [--commit REV] [-D...]
+       lz_window_isa.py --diff REV [--api NAME ...] [-D...]
 
 Compiles api/<format>_api.hip for the device only with the product's flags (plus any -D given), once as it is and once
 with -DNVCOMP_LZW_RUNS=0 -- the kernel then holds only the instance of the decode loop without the run executor, the one
@@ -9,8 +10,15 @@ the mix runs -- and prints for <format>_decompress_window_kernel<true> of each: 
 (v_*), all vector-side instructions (v_*, ds_*, global_*, flat_*, buffer_*, scratch_*), v_mov_b32 / v_mov_b64, s_waitcnt,
 materialised ballots (v_cndmask_b32 v, 0, 1, mask whose only use is the v_cmp_ne_u32 0, v behind it), and the SGPR spill /
 VGPR / scratch figures of the kernel's metadata. --commit counts the sources of that revision instead of the working tree.
+
+--diff REV compiles api/NAME.hip (default: lz4_api snappy_api) from REV and from the working tree, each with the product's
+flags for that file plus any -D given, and compares the text of every function of the two -- the kernels with their
+.amdhsa_kernel descriptor, and the functions they call -- ignoring lines that hold the per-build __hip_cuid_ symbol and
+the per-file numbering of local labels. One line per function: identical, different (instructions a / b), only in REV,
+only in worktree; the exit status is 1 when any is different. This is how a refactor shows that it left the code alone.
 """
 import argparse
+import concurrent.futures
 import json
 import os
 import re
@@ -64,28 +72,92 @@ def count(body, meta):
     }
 
 
+# What csrc/Makefile adds to CXXFLAGS for single files.
+PRODUCT_FLAGS = {"lz4_api": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+                 "snappy_api": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+                 "bitcomp_native_api": ["-fhip-fp32-correctly-rounded-divide-sqrt"]}
+
+
+def checkout(rev, tmp):
+    """The sources of `rev` unpacked under `tmp`, or the repository itself for the working tree."""
+    if not rev:
+        return REPO
+    root = os.path.join(tmp, "src")
+    os.makedirs(root)
+    tar = subprocess.run(["git", "-C", REPO, "archive", rev, "nvcomp_amd/csrc", "include"], check=True,
+                         stdout=subprocess.PIPE).stdout
+    subprocess.run(["tar", "-x", "-C", root], input=tar, check=True)
+    return root
+
+
+def compile_asm(root, api, flags, out):
+    src = os.path.join(root, "nvcomp_amd", "csrc")
+    subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O3", "-std=c++17", "--offload-arch=gfx950",
+                    *PRODUCT_FLAGS.get(api, []), "--cuda-device-only", "-S",
+                    "-I" + os.path.join(root, "include"), "-I" + src, "-Wno-unused-function", *flags,
+                    os.path.join(src, "api", f"{api}.hip"), "-o", out], check=True)
+    return open(out).read()
+
+
+def functions(asm):
+    """{symbol: text} of every function; a kernel's text ends with its .amdhsa_kernel descriptor."""
+    asm = "\n".join(ln for ln in asm.splitlines() if "__hip_cuid_" not in ln)
+    asm = re.sub(r"(\.L[A-Za-z_]+|\bBB)\d+_", r"\1_", asm)  # .LBB<function number>_<block>, and BB<n>_<block> in comments
+    asm = re.sub(r"(\.Lfunc_(?:begin|end))\d+", r"\1", asm)
+    out = {}
+    for m in re.finditer(r"^\t\.type\t(\w+),@function\n", asm, re.M):
+        sym = m.group(1)
+        out[sym] = asm[asm.index(sym + ":", m.end()): asm.index(".Lfunc_end", m.end())]
+        desc = re.search(r"^\t\.amdhsa_kernel %s\n.*?\.end_amdhsa_kernel" % sym, asm, re.M | re.S)
+        if desc:
+            out[sym] += desc.group(0)
+    return out
+
+
+def instructions(body):
+    return sum(1 for ln in body.splitlines() if ln.startswith("\t") and not ln.lstrip().startswith((".", ";")) and ln.strip())
+
+
+def diff(rev, apis, extra, keep):
+    with tempfile.TemporaryDirectory() as tmp:
+        roots = {rev: checkout(rev, tmp), "worktree": REPO}
+        jobs = [(api, side) for api in apis for side in roots]
+        with concurrent.futures.ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as pool:
+            texts = dict(zip(jobs, pool.map(lambda j: functions(compile_asm(
+                roots[j[1]], j[0], extra, os.path.join(keep or tmp, f"{j[0]}_{j[1].replace('/', '_')}.s"))), jobs)))
+    different = 0
+    for api in apis:
+        old, new = texts[api, rev], texts[api, "worktree"]
+        for sym in sorted(set(old) | set(new)):
+            name = subprocess.run(["c++filt", "-p", sym], stdout=subprocess.PIPE, text=True).stdout.strip()
+            if sym not in new:
+                verdict = f"only in {rev}"
+            elif sym not in old:
+                verdict = "only in worktree"
+            elif old[sym] == new[sym]:
+                verdict = "identical"
+            else:
+                verdict = f"different (instructions {instructions(old[sym])} / {instructions(new[sym])})"
+                different += 1
+            print(f"{api}: {name}: {verdict}")
+    return 1 if different else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--format", default="lz4", choices=("lz4", "snappy"))
     ap.add_argument("--commit", default=None)
+    ap.add_argument("--diff", default=None, metavar="REV")
+    ap.add_argument("--api", nargs="+", default=["lz4_api", "snappy_api"])
     ap.add_argument("--keep", default=None, help="directory to keep the .s files in")
     a, extra = ap.parse_known_args()
+    if a.diff:
+        return diff(a.diff, a.api, extra, a.keep)
     with tempfile.TemporaryDirectory() as tmp:
-        root = REPO
-        if a.commit:
-            root = os.path.join(tmp, "src")
-            os.makedirs(root)
-            tar = subprocess.run(["git", "-C", REPO, "archive", a.commit, "nvcomp_amd/csrc", "include"], check=True,
-                                 stdout=subprocess.PIPE).stdout
-            subprocess.run(["tar", "-x", "-C", root], input=tar, check=True)
-        src = os.path.join(root, "nvcomp_amd", "csrc")
+        root = checkout(a.commit, tmp)
         for label, flags in (("kernel", []), ("non_runs_loop", ["-DNVCOMP_LZW_RUNS=0"])):
-            out = os.path.join(a.keep or tmp, f"{a.format}_{label}.s")
-            subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O3", "-std=c++17", "--offload-arch=gfx950",
-                            "-mllvm", "-amdgpu-sched-strategy=max-ilp", "--cuda-device-only", "-S",
-                            "-I" + os.path.join(root, "include"), "-I" + src, "-Wno-unused-function", *flags, *extra,
-                            os.path.join(src, "api", f"{a.format}_api.hip"), "-o", out], check=True)
-            body, meta = kernel_text(open(out).read(), f"{a.format}_decompress_window_kernel")
+            asm = compile_asm(root, f"{a.format}_api", [*flags, *extra], os.path.join(a.keep or tmp, f"{a.format}_{label}.s"))
+            body, meta = kernel_text(asm, f"{a.format}_decompress_window_kernel")
             print(json.dumps({"format": a.format, "what": label, "commit": a.commit or "worktree", **count(body, meta)}))
 
 

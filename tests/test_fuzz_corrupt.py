@@ -82,7 +82,7 @@ def test_corrupt_streams_are_contained(backend, lz_path, oracle, fmt):
 
 @pytest.mark.parametrize("fmt", ["LZ4", "Snappy"])
 def test_corrupt_column_streams_are_contained(backend, lz_path, oracle, fmt):
-    """The same on the data the run executor takes (common/lz_window.hip.h: execute_run_batch; chunks that shrank 8 x go
+    """The same on the data the run executor takes (common/lz_run_batch.hip.h: execute_run_batch; chunks that shrank 8 x go
     through the loop that holds it): sorted-key and int32 columns through liblz4 (default and HC) / libsnappy, damaged --
     offsets that stop being multiples of the period, lengths that overshoot the chunk, periods that change under a run,
     a speculated match whose source moved. Canaries behind every slot; an accepted stream decodes like the CPU oracle's."""

@@ -16,7 +16,7 @@ UNIQUE_MIB = 64
 REPLICAS = 16  # 16 x 1 024 chunks = 16 384 chunks, 1 GiB of output, every replica in device memory of its own
 
 
-# (format, dataset, producer): the headline mix; and, since round 6, the columns the run executor takes (common/lz_window.hip.h:
+# (format, dataset, producer): the headline mix; and, since round 6, the columns the run executor takes (common/lz_run_batch.hip.h:
 # execute_run_batch) -- the sorted-key column through liblz4 HC (clean runs) and through its default compressor (every run
 # starts with a match from far back: the speculated matches), the int32 column -- at the same batch size
 CASES = [("LZ4", "silesia_style", "hc"), ("Snappy", "silesia_style", "snappy"), ("LZ4", "mortgage_col0_like", "hc"),

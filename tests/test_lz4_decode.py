@@ -154,7 +154,7 @@ def _lz4_expand(seqs, tail):
 
 def test_streamed_long_runs(backend, lz_path, oracle):
     """Long literal runs and long matches leave the window path and are written straight to the output buffer
-    (common/lz_window.hip.h: stream_sequence): every period class (a register tile that never changes, one that rotates,
+    (common/lz_stream.hip.h: stream_sequence): every period class (a register tile that never changes, one that rotates,
     HBM-to-HBM copies whose effective offset doubles), lengths around the thresholds and the step sizes, every output
     alignment, short sequences in between (the window restarts behind a streamed one)."""
     rng = np.random.RandomState(77)
@@ -202,7 +202,7 @@ def _run_blocks(rng, n_seqs, offs, lit_choices, mlen_choices, first_lit=16):
 
 def test_run_batches(backend, lz_path, oracle):
     """Sequences of "a few literals, then a match of period 1, 2, 4, 8 or 16" -- sorted key columns, typed columns -- are
-    executed up to 64 at a time straight to the output buffer (common/lz_window.hip.h: execute_run_batch): every period,
+    executed up to 64 at a time straight to the output buffer (common/lz_run_batch.hip.h: execute_run_batch): every period,
     0 .. 16 literals (17 and more end the batch), runs from 16 bytes on (shorter ones end it), sequences without literals
     that continue the run in front of them (merged), a period that changes, batches at every alignment of the output
     buffer, at the start and at the end of a chunk, and behind / in front of ordinary sequences."""
@@ -259,7 +259,7 @@ def test_run_batches(backend, lz_path, oracle):
 def test_run_batches_speculated_matches(backend, lz_path, oracle):
     """liblz4's fast compressor starts a run of equal keys with a short match from far back -- the new key's unchanged bytes,
     copied from an earlier key, at a distance that is a multiple of the period. The run executor takes such a match for
-    bytes the run would have produced anyway and checks that against the patterns (common/lz_window.hip.h:
+    bytes the run would have produced anyway and checks that against the patterns (common/lz_run_batch.hip.h:
     execute_run_batch): matches that hold and matches that do not (the key's high bytes changed in between), sources in
     this batch, in front of it, across a run boundary and inside literals, short and long ones, periods 4, 8 and 16; the
     real column through liblz4; and a distance beyond the output, which must come back as an error, not as bytes."""
@@ -356,7 +356,7 @@ def test_two_byte_length_fields(backend, lz_path, oracle):
 
 
 def test_stream_ends_on_ring_block_boundaries(backend, lz_path, oracle):
-    """The end of a chunk against the stream ring's geometry (common/lz_window.hip.h): the ring is refilled in 1 KiB blocks of
+    """The end of a chunk against the stream ring's geometry (common/lz_ring.hip.h): the ring is refilled in 1 KiB blocks of
     the chunk's 16-byte-aligned coordinates, bytes behind the chunk's end read as zero inside the last loaded block and as
     OLDER stream bytes when the chunk ends exactly on a block boundary, and the token chase's last windows must not let
     either leak into a token position. Blocks whose last byte lies on, right before and right behind such a boundary, for

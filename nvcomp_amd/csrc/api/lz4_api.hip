@@ -13,9 +13,9 @@
 #include "nvcomp/amd_ext.h"
 
 #include "common/lz_api.hip.h"
-#include "lz4/lz4_decode.hip.h"
 #include "lz4/lz4_decode_window.hip.h"
 #include "lz4/lz4_encode.hip.h"
+#include "lz4/lz4_size.hip.h"
 
 namespace {
 
@@ -137,7 +137,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) lz4_decompress_size_kerne
 {
   lzl::decompress_size(comp_ptrs, comp_bytes, uncompressed_bytes, batch_size, [](const uint8_t* in, uint32_t in_len) -> uint32_t {
     uint32_t err = lz::kErrNone;
-    const uint32_t produced = lz4::decode_chunk<false, true, true>(in, in_len, nullptr, 0, err);
+    const uint32_t produced = lz4::decoded_size(in, in_len, err);
     return err ? 0 : produced;
   });
 }

@@ -11,6 +11,40 @@
 
 namespace {
 
+/* The self-test's probe of a copy that reads what the same wave has just written to global memory: the LZ77 match
+ * copy d[i] = d[i - off], i in [0,len), byte-serial semantics
+ * (off < len replicates a pattern). The effective offset E is kept a multiple
+ * of off and doubled as the pattern grows, so that a whole wave-wide step
+ * (64 lanes x 16 / 4 / 1 bytes) never reads a byte the same step writes. */
+__device__ __forceinline__ void wave_match_copy(uint8_t* d, uint32_t off, uint32_t len)
+{
+  const uint32_t lane = (uint32_t)wave::fresh_lane_id();
+  uint32_t done = 0;
+  uint32_t E = off;
+  while (done < len) {
+    while (E < 1024 && 2 * E <= done + off) {
+      E *= 2;
+    }
+    const uint32_t rem = len - done;
+    if (E >= 1024 && rem >= 1024) {
+      lz::copy16(d + done + lane * 16, d + done + lane * 16 - E);
+      done += 1024;
+    } else if (E >= 256 && rem >= 256) {
+      lz::st_u32(d + done + lane * 4, lz::ld_u32(d + done + lane * 4 - E));
+      done += 256;
+    } else {
+      uint32_t n = E < 64 ? E : 64;
+      n = n < rem ? n : rem;
+      if (lane < n) {
+        uint8_t* t = d + done + lane; /* pointer arithmetic: done + lane - E is negative as an index */
+        *t = *(t - E);
+      }
+      done += n;
+    }
+    wave::sync();
+  }
+}
+
 __global__ void __launch_bounds__(64) wave_selftest_kernel(const uint32_t* in, uint32_t* out, uint8_t* scratch)
 {
   const uint32_t lane = (uint32_t)wave::lane_id();
@@ -33,7 +67,7 @@ __global__ void __launch_bounds__(64) wave_selftest_kernel(const uint32_t* in, u
     scratch[64 + lane] = (uint8_t)(10 + lane);
   }
   wave::sync();
-  lz::wave_match_copy(scratch + 67, 3, 3000);
+  wave_match_copy(scratch + 67, 3, 3000);
   wave::sync();
   uint32_t bad = 0;
   for (uint32_t i = lane; i < 3003; i += 64) {

@@ -13,9 +13,9 @@
 #include "nvcomp/amd_ext.h"
 
 #include "common/lz_api.hip.h"
-#include "snappy/snappy_decode.hip.h"
 #include "snappy/snappy_decode_window.hip.h"
 #include "snappy/snappy_encode.hip.h"
+#include "snappy/snappy_preamble.hip.h"
 
 namespace {
 

@@ -1,6 +1,6 @@
 /*
- * common/lz_copy.hip.h -- the copy primitives of the LZ decoders: clamped dword copies in LDS, far-match
- * loads and stores, overlapping (periodic) match copies.
+ * common/lz_copy.hip.h -- the copy primitives of the LZ decoders: clamped dword copies in LDS, the aligned
+ * store of far-match data, overlapping (periodic) match copies.
  */
 #pragma once
 
@@ -76,30 +76,6 @@ __device__ __forceinline__ void copy_dwords_clamped_disjoint(uint8_t* dst, const
   }
 }
 
-/* Same, for sources that must all be fetched before anything is written
- * (HBM gathers: one round trip for the whole batch). */
-template <uint32_t STEPS>
-__device__ __forceinline__ void load_dwords_clamped(uint32_t (&buf)[8], const uint8_t* src, uint32_t len)
-{
-  const uint32_t last = len - 4;
-#pragma unroll
-  for (uint32_t i = 0; i < STEPS; ++i) {
-    const uint32_t o = 4 * i < last ? 4 * i : last;
-    buf[i] = wave::gload_u32(src + o);
-  }
-}
-
-template <uint32_t STEPS>
-__device__ __forceinline__ void store_dwords_clamped(uint8_t* dst, const uint32_t (&buf)[8], uint32_t len)
-{
-  const uint32_t last = len - 4;
-#pragma unroll
-  for (uint32_t i = 0; i < STEPS; ++i) {
-    const uint32_t o = 4 * i < last ? 4 * i : last;
-    lz::st_u32(dst + o, buf[i]);
-  }
-}
-
 /* Far-match data (registers) into the window with aligned accesses only: dst sits h = 1..4 bytes into the
  * aligned frame that starts at dst - h (h = 4: dst itself is aligned). d[] = the match's sequential dwords,
  * l4 = its last 4 bytes. Up to 3 head bytes, whole aligned dwords, up to 3 tail bytes. */
@@ -134,19 +110,6 @@ __device__ __forceinline__ void far_store_aligned(uint8_t* dst, const uint32_t (
       tp[b] = (uint8_t)(tv >> (8 * b));
     }
   }
-}
-
-/* sequential (unclamped) dwords of a far match plus its last 4 bytes; reads up to 3 bytes past the match */
-template <uint32_t STEPS>
-__device__ __forceinline__ void far_load_seq(uint32_t (&buf)[8], uint32_t& l4, const uint8_t* src, uint32_t len)
-{
-#pragma unroll
-  for (uint32_t i = 0; i < STEPS; ++i) {
-    if (4 * i < len) {
-      buf[i] = wave::gload_u32(src + 4 * i);
-    }
-  }
-  l4 = wave::gload_u32(src + len - 4);
 }
 
 /* x / off == umulhi(x, kMagic.v[off]) for x < 2^16 and 2 <= off < 256 (the runs' periods): a table instead of the 32-bit

@@ -52,9 +52,9 @@ constexpr uint32_t kLdsBytes = 64 * kStride + 512;     /* of the wave's LDS, fre
 constexpr uint32_t kTail = kBlock + 8;                 /* the last bytes of a chunk are never indexed (no load passes its end) */
 constexpr uint32_t kMinStream = 2048;                  /* shorter streams are not worth an index */
 constexpr uint32_t kMaxStream = 0xffffu;               /* positions are stored in 16 bits */
-constexpr uint32_t kLaneCap = 344; /* (a multiple of 4: positions are stored four at a time) */
-constexpr uint32_t kLaneCapUnused = 0;                     /* positions a lane's list holds: a segment is at most 1 023 bytes, a
-                                                        * sequence at least 3 (Snappy: 2 -- a lane that fills its list stops) */
+constexpr uint32_t kLaneCap = 344;                     /* positions a lane's list holds: a segment is at most 1 023 bytes, a
+                                                        * sequence at least 3 (Snappy: 2 -- a lane that fills its list stops);
+                                                        * a multiple of 4: positions are stored four at a time */
 constexpr size_t kScratchPerWave = 2 * 64 * (size_t)kLaneCap;
 constexpr uint32_t kNone = 0xffffffffu;
 

@@ -53,7 +53,6 @@ constexpr uint32_t kQueue = 4 * kStep;   /* hit queue: (position in the step) | 
 constexpr uint32_t kResults = kStep;     /* one byte per position: the match length of a hit that was measured through the queue */
 constexpr uint32_t kScratch = kQueue + kResults;
 constexpr uint32_t kCap = 24;            /* per-lane match measurement (longer matches: the whole wave, lzm::extend_match) */
-constexpr uint32_t kBack = 4;            /* bytes a match may grow backwards over its literal run: what the word check brings */
 constexpr uint32_t kLdsPerWave = 2 * kEntries + kImage + kScratch;
 
 __device__ __forceinline__ uint32_t hashw(uint32_t v)

@@ -197,12 +197,6 @@ __device__ __forceinline__ void in_ensure(InRing& r, uint32_t q, uint32_t want_h
   }
 }
 
-template <class R>
-__device__ __forceinline__ bool in_resident(const R& r, uint32_t v_lo, uint32_t v_hi)
-{
-  return v_lo >= r.lo && v_hi <= r.hi;
-}
-
 /* Byte at virtual position v (per lane): LDS when resident, HBM otherwise. The stream type R is lzw::InRing (a wave's
  * ring over the chunk) or lzt::Stream (common/lz_team.hip.h: the whole chunk staged in LDS, kMask = all ones). */
 template <class R>

@@ -1,7 +1,9 @@
 /*
- * lz4/lz4_decode_window.hip.h -- LZ4 block decoder on the LDS-staged executor
- * (common/lz_window.hip.h). Same entry-point contract as lz4_decode.hip.h; this
- * is the default nvcompBatchedLZ4DecompressAsync path.
+ * lz4/lz4_decode_window.hip.h -- the LZ4 block decoder, on the LDS-staged executor
+ * (common/lz_window.hip.h): what nvcompBatchedLZ4DecompressAsync runs, one wave per
+ * chunk here, two waves or a workgroup per chunk through common/lz_pair.hip.h and
+ * common/lz_team.hip.h with this file's front end. decode_chunk() returns the bytes
+ * produced, 0 with an error bit for a chunk it rejects. (The block format: lz4_size.hip.h.)
  *
  * Token chase: the next 256 stream positions are examined in parallel -- lane l
  * of register j assumes a token starts at position wb + 64 j + l and computes

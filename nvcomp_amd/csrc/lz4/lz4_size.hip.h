@@ -1,12 +1,11 @@
 /*
- * lz4/lz4_decode.hip.h -- batched LZ4 block-format decoder for gfx950.
- *
- * Replaces the device side of nvcompBatchedLZ4DecompressAsync and
- * nvcompBatchedLZ4GetDecompressSizeAsync (reference call sites:
- * benchmarks/benchmark_template_chunked.cuh:520-530,
- * examples/lz4_cpu_compression.cu:121-131,
- * examples/low_level_quickstart_example.cpp:112-117). One wavefront per chunk;
- * see common/lz_common.hip.h for the execution model.
+ * lz4/lz4_size.hip.h -- what an LZ4 block decodes to, for nvcompBatchedLZ4GetDecompressSizeAsync: an LZ4 block does not
+ * say, so one wavefront walks the chunk's token chain and sums the lengths. Nothing is written.
+ *   1. chase - the wave walks the token chain with wave-uniform (scalar) arithmetic over a 256-byte register window and
+ *              records the start of up to 64 sequences;
+ *   2. parse - lane k decodes the fields of sequence k and checks them against the end of the chunk;
+ *   3. sum   - the batch's lengths are added up across the wave.
+ * The decoders proper are in lz4_decode_window.hip.h.
  *
  * Block format (public LZ4 specification; checked against liblz4 in tests):
  *   token: hi nibble = literal length, lo nibble = match length - 4; a nibble
@@ -20,6 +19,63 @@
 
 namespace lz4 {
 
+/* ---- 256-byte register window over the compressed stream ------------------
+ * Lane l holds the aligned dword at "virtual position" wb + 4l, where virtual
+ * position = byte index in the chunk + (chunk address & 3). A wave-uniform byte
+ * is fetched with one v_readlane and scalar shifts: no memory round trip on the
+ * token chain. */
+struct InWindow
+{
+  const uint8_t* base; /* chunk pointer rounded down to 4 bytes (uniform) */
+  uint32_t vbeg;       /* virtual position of the first chunk byte: chunk & 3 */
+  uint32_t vend;       /* vbeg + chunk length */
+  uint32_t wb;         /* virtual position of lane 0's dword (multiple of 4) */
+  uint32_t cw;         /* this lane's dword */
+};
+
+__device__ __forceinline__ void window_init(InWindow& w, const uint8_t* in, uint32_t in_len)
+{
+  const uint32_t a = (uint32_t)((uintptr_t)in & 3u);
+  w.base = in - a;
+  w.vbeg = a;
+  w.vend = a + in_len;
+  w.wb = 0;
+  w.cw = 0;
+}
+
+/* (Re)load the window so that it starts at the dword containing virtual
+ * position q. Bytes outside the chunk read as zero and are never fetched. */
+__device__ __forceinline__ void window_load(InWindow& w, uint32_t q)
+{
+  w.wb = q & ~3u;
+  const uint32_t v = w.wb + 4u * (uint32_t)wave::lane_id();
+  uint32_t x = 0;
+  if (v >= w.vbeg && v + 4 <= w.vend) {
+    x = *(const uint32_t*)(w.base + v);
+  } else if (v + 4 > w.vbeg && v < w.vend) {
+    for (uint32_t j = 0; j < 4; ++j) {
+      if (v + j >= w.vbeg && v + j < w.vend) {
+        x |= (uint32_t)w.base[v + j] << (8 * j);
+      }
+    }
+  }
+  w.cw = x;
+}
+
+__device__ __forceinline__ bool window_has(const InWindow& w, uint32_t q)
+{
+  return q - w.wb < 256u;
+}
+
+/* Byte at virtual position q (uniform; must be inside the window). */
+__device__ __forceinline__ uint32_t window_byte(const InWindow& w, uint32_t q)
+{
+  const uint32_t r = q - w.wb;
+  return (wave::read_lane(w.cw, r >> 2) >> ((r & 3u) * 8u)) & 0xffu;
+}
+
+/* ---- the token chase ------------------------------------------------------ */
+
 /* For each of the 4 token candidates in a dword: distance to the next token if
  * neither nibble needs extension bytes (1 token + L literals + 2 offset), else 0. */
 __device__ __forceinline__ uint32_t fast_deltas(uint32_t cw)
@@ -32,20 +88,20 @@ __device__ __forceinline__ uint32_t fast_deltas(uint32_t cw)
 
 struct Chase
 {
-  lz::InWindow w;
+  InWindow w;
   uint32_t dv; /* fast_deltas of the window */
   uint32_t q;  /* virtual position of the next token (uniform) */
 };
 
 __device__ __forceinline__ void chase_reload(Chase& c, uint32_t q)
 {
-  lz::window_load(c.w, q);
+  window_load(c.w, q);
   c.dv = fast_deltas(c.w.cw);
 }
 
 __device__ __forceinline__ void chase_init(Chase& c, const uint8_t* in, uint32_t in_len)
 {
-  lz::window_init(c.w, in, in_len);
+  window_init(c.w, in, in_len);
   c.q = c.w.vbeg;
   chase_reload(c, c.q);
 }
@@ -56,7 +112,7 @@ __device__ __forceinline__ void chase_init(Chase& c, const uint8_t* in, uint32_t
 __device__ __forceinline__ uint32_t chase_slow_next(Chase& c)
 {
   const uint32_t vend = c.w.vend;
-  const uint32_t t = lz::window_byte(c.w, c.q);
+  const uint32_t t = window_byte(c.w, c.q);
   uint32_t pos = c.q + 1;
   uint32_t lit = t >> 4;
   if (lit == 15) {
@@ -64,10 +120,10 @@ __device__ __forceinline__ uint32_t chase_slow_next(Chase& c)
       if (pos >= vend) {
         return vend + 1;
       }
-      if (!lz::window_has(c.w, pos)) {
+      if (!window_has(c.w, pos)) {
         chase_reload(c, pos);
       }
-      const uint32_t b = lz::window_byte(c.w, pos);
+      const uint32_t b = window_byte(c.w, pos);
       ++pos;
       lit += b;
       if (b != 255) {
@@ -84,10 +140,10 @@ __device__ __forceinline__ uint32_t chase_slow_next(Chase& c)
       if (pos >= vend) {
         return vend + 1;
       }
-      if (!lz::window_has(c.w, pos)) {
+      if (!window_has(c.w, pos)) {
         chase_reload(c, pos);
       }
-      const uint32_t b = lz::window_byte(c.w, pos);
+      const uint32_t b = window_byte(c.w, pos);
       ++pos;
       if (b != 255) {
         break;
@@ -98,12 +154,12 @@ __device__ __forceinline__ uint32_t chase_slow_next(Chase& c)
 }
 
 /* Record the virtual start positions of the next (up to 64) sequences:
- * lane k of seqpos <- start of sequence k. Returns the count (<= max_count <= 64). */
-__device__ __forceinline__ uint32_t chase(Chase& c, uint32_t& seqpos, uint32_t max_count)
+ * lane k of seqpos <- start of sequence k. Returns the count. */
+__device__ __forceinline__ uint32_t chase(Chase& c, uint32_t& seqpos)
 {
   uint32_t k = 0;
-  while (k < max_count && c.q < c.w.vend) {
-    if (!lz::window_has(c.w, c.q)) {
+  while (k < 64u && c.q < c.w.vend) {
+    if (!window_has(c.w, c.q)) {
       chase_reload(c, c.q);
     }
     const uint32_t r = c.q - c.w.wb;
@@ -115,7 +171,10 @@ __device__ __forceinline__ uint32_t chase(Chase& c, uint32_t& seqpos, uint32_t m
   return k;
 }
 
-/* Lane-parallel field decode of the sequence whose token is at in[p]. */
+/* ---- one sequence --------------------------------------------------------- */
+
+/* Lane-parallel field decode of the sequence whose token is at in[p]; the walker reads the two lengths. `bad`: the
+ * sequence does not fit the chunk, or no token follows its match. */
 __device__ __forceinline__ void parse(
     const uint8_t* __restrict__ in, uint32_t in_len, uint32_t p, bool active, lz::Seq& s, bool& bad)
 {
@@ -180,10 +239,8 @@ __device__ __forceinline__ void parse(
   s.match_len = mlen + 4;
 }
 
-/* Decode one chunk with the calling wave. Returns bytes produced, 0 on error. */
-template <bool CHECKED, bool LANE_PARALLEL, bool SIZE_ONLY>
-__device__ __forceinline__ uint32_t decode_chunk(
-    const uint8_t* __restrict__ in, uint32_t in_len, uint8_t* out, uint32_t out_cap, uint32_t& err)
+/* What the chunk decodes to, by the calling wave; 0 and an error bit for a block that is malformed or too large. */
+__device__ __forceinline__ uint32_t decoded_size(const uint8_t* __restrict__ in, uint32_t in_len, uint32_t& err)
 {
   const uint32_t lane = (uint32_t)wave::lane_id();
   uint32_t op = 0;
@@ -195,9 +252,7 @@ __device__ __forceinline__ uint32_t decode_chunk(
   chase_init(c, in, in_len);
   while (c.q < c.w.vend) {
     uint32_t seqpos = 0;
-    /* LANE_PARALLEL = false is the ablation baseline: one sequence per step,
-     * every copy done by the whole wave. */
-    const uint32_t count = chase(c, seqpos, LANE_PARALLEL ? 64u : 1u);
+    const uint32_t count = chase(c, seqpos);
     lz::Seq s;
     bool bad;
     parse(in, in_len, seqpos - c.w.vbeg, lane < count, s, bad);
@@ -205,22 +260,15 @@ __device__ __forceinline__ uint32_t decode_chunk(
       err |= lz::kErrInput;
       return 0;
     }
-    if (SIZE_ONLY) {
-      /* a hostile stream may claim lengths whose 32-bit sum wraps to a small bogus size: the batch is summed in two
-       * 16-bit halves (64 x 65535 fits) and the total checked against the largest chunk any decoder here accepts */
-      const uint32_t len = s.lit_len + s.match_len; /* each part is at most 2^30 */
-      const uint64_t batch = (uint64_t)wave::reduce_add(len & 0xffffu) + ((uint64_t)wave::reduce_add(len >> 16) << 16);
-      if (batch + op > (1u << 26)) {
-        err |= lz::kErrOutput;
-        return 0;
-      }
-      op += (uint32_t)batch;
-    } else {
-      op += lz::execute_batch<CHECKED, LANE_PARALLEL>(in, in_len, out, out_cap, op, count, s, err);
-      if (CHECKED && err) {
-        return 0;
-      }
+    /* a hostile stream may claim lengths whose 32-bit sum wraps to a small bogus size: the batch is summed in two
+     * 16-bit halves (64 x 65535 fits) and the total checked against the largest chunk any decoder here accepts */
+    const uint32_t len = s.lit_len + s.match_len;
+    const uint64_t batch = (uint64_t)wave::reduce_add(len & 0xffffu) + ((uint64_t)wave::reduce_add(len >> 16) << 16);
+    if (batch + op > (1u << 26)) {
+      err |= lz::kErrOutput;
+      return 0;
     }
+    op += (uint32_t)batch;
   }
   return op;
 }

@@ -5,13 +5,20 @@
  * lz4_decode_window.hip.h: 256 speculative tag positions per reload, one
  * v_readlane per element; literals with a multi-byte length field are resolved
  * in the speculative pass as well (the length bytes sit right behind the tag).
+ *
+ * Raw format (public Snappy format description; checked against libsnappy):
+ *   varint32 uncompressed length, then elements tagged by (tag & 3):
+ *   0 literal (len-1 = tag>>2, or in the next 1..4 bytes when tag>>2 is 60..63),
+ *   1 copy with 11-bit offset (len 4..11), 2 copy with 16-bit offset (len 1..64),
+ *   3 copy with 32-bit offset (len 1..64). All four kinds are decoded, whatever
+ *   the producing compressor chose to emit (CHANGELOG.md:182-184).
  */
 #pragma once
 
 #include "common/lz_window.hip.h"
 #include "common/lz_chase.hip.h"
 #include "common/lz_run_batch.hip.h"
-#include "snappy/snappy_decode.hip.h"
+#include "snappy/snappy_preamble.hip.h"
 
 namespace snappyw {
 

@@ -478,6 +478,76 @@ def test_get_decompress_size(backend, oracle):
     assert sizes.tolist() == [oracle.lz4_decompressed_size(c) for c in comp]
 
 
+def _size_query_cases(with_largest_chunk):
+    """[(what, block, size the query must give)] for the LZ4 size walker: 0 for a malformed block, else the sum of the
+    lengths the builder wrote."""
+    rng = np.random.RandomState(909)
+
+    def lits(n):
+        return rng.randint(0, 256, size=n).astype(np.uint8).tobytes()
+
+    def chain(n):
+        return [(lits(3), 1, 5)] + [(lits(j % 3), 1 + j % 2, 4 + j % 9) for j in range(1, n)]
+
+    def total(seqs, tail):
+        return sum(len(l) + m for l, _, m in seqs) + len(tail)
+
+    cases = []
+    # the walker takes up to 64 sequences a batch; the final literal-only sequence counts
+    for n in (64, 65, 128, 129):
+        seqs, tail = chain(n - 1), lits(7)
+        cases.append((f"{n} sequences", _lz4_block(seqs, tail), total(seqs, tail)))
+    # a token in the last byte of the first 256-byte register window, its literal-length extension byte(s) behind it; the
+    # window starts at the chunk's address rounded down to 4 bytes, so one of the four positions is that byte
+    for p in (252, 253, 254, 255):
+        n0 = (p - 3) % 3 or 3
+        head = [(lits(n0), 1, 4)] + [(b"", 1, 4)] * ((p - 3 - n0) // 3)
+        assert _lz4_block(head, b"").size - 1 == p
+        for nlit in (20, 15 + 255 + 3):
+            seqs, tail = head + [(lits(nlit), 9, 6), (lits(2), 1, 4)], lits(9)
+            block = _lz4_block(seqs, tail)
+            assert block[p] >> 4 == 15
+            cases.append((f"token at byte {p}, {nlit} literals", block, total(seqs, tail)))
+    # literal lengths of three and four extension bytes, in the middle and in the final sequence
+    seqs, tail = [(lits(3), 1, 4), (lits(15 + 2 * 255), 7, 10), (lits(15 + 3 * 255 + 7), 2, 30)], lits(15 + 2 * 255 + 75)
+    cases.append(("literal runs of 525, 787 and 600 bytes", _lz4_block(seqs, tail), total(seqs, tail)))
+    # a block that ends where it may not, in the first batch of the walker and in the second
+    for n in (1, 70):
+        head = bytes(_lz4_block(chain(n), b"")[:-1])  # well-formed sequences, the last one's match at the very end
+        for what, cut in (("behind a match", b""),
+                          ("where a literal length byte must follow", b"\xf0"),
+                          ("behind a literal length byte of 255", b"\xf0\xff"),
+                          ("inside 5 literals", b"\x50ab"),
+                          ("inside 300 literals", b"\xf0\xff\x1e" + lits(100)),
+                          ("inside the offset", b"\x20ab\x01"),
+                          ("where a match length byte must follow", b"\x1fa\x01\x00"),
+                          ("behind a match length byte of 255", b"\x1fa\x01\x00\xff")):
+            cases.append((f"{n} sequences, then cut off {what}", np.frombuffer(head + cut, dtype=np.uint8), 0))
+    # the walker's overflow guard: more than 2^26 bytes is no chunk of any decoder here; exactly 2^26 still is one. Either
+    # takes 263 172 length bytes, seven seconds of the emulator's time, which therefore walks only the one that is too long
+    for over in ((0, 1) if with_largest_chunk else (1,)):
+        seqs, tail = [(b"abc", 1, (1 << 26) - 8 + over)], b"12345"
+        cases.append((f"a match that brings the block to 2^26 + {over} bytes", _lz4_block(seqs, tail),
+                      0 if over else total(seqs, tail)))
+    return cases
+
+
+def test_get_decompress_size_of_hand_built_blocks(backend, oracle):
+    """The size query walks the token chain by itself (lz4/lz4_size.hip.h): batches of exactly 64 and 65 sequences, a token
+    whose length bytes lie behind the reload of the 256-byte register window, lengths of three and more extension bytes,
+    blocks cut off inside a length field, the literals or the offset (size 0), and a match whose length bytes claim more
+    than 2^26 bytes (size 0). Once tightly packed and once at 16-byte-aligned addresses."""
+    cases = _size_query_cases(with_largest_chunk=backend.name == "gpu")
+    for what, b, want in cases:
+        if want or "cut off" in what:  # the oracle sums without an upper limit: not asked about the overflow case
+            assert oracle.lz4_decompressed_size(b) == want, what
+    for align in (1, 16):
+        sizes = backend.codec("LZ4").get_decompress_size([b for _, b, _ in cases], comp_align=align).tolist()
+        for (what, _, want), got in zip(cases, sizes):
+            assert got == want, f"{what} (chunks aligned to {align}): {got}, expected {want}"
+        cases = [c for c in cases if c[1].size < (1 << 16)]  # the length bytes of 2^26 are walked once
+
+
 def test_runs_executed_by_the_whole_wave(backend, lz_path, oracle):
     """A few literals and a long match of period 1 .. 16 -- the shape of sorted key columns: trains of such sequences, runs at
     the very start of a chunk, runs whose literals are 0 .. 32 bytes, ordinary sequences in between; a run that ends behind

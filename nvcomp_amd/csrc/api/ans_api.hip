@@ -1,13 +1,15 @@
 /*
  * api/ans_api.hip -- C ABI of the batched ANS codec (include/nvcomp/ans.h) and the kernels
  * it launches: one wavefront per chunk, one launch per *Async call on the caller's stream;
- * nothing here allocates or synchronises.
+ * nothing here allocates or synchronises. The compress and size-query frames and the argument
+ * checks are common/api_batch.hip.h; the decode kernel spells its frame out, because the compiler
+ * writes it differently otherwise (profiles/api_frame_shared.md).
  */
 #include <hip/hip_runtime.h>
 
 #include "nvcomp/ans.h"
 
-#include "common/api_launch.h"
+#include "common/api_batch.hip.h"
 #include "common/log.h"
 
 #include "ans/ans.hip.h"
@@ -24,18 +26,10 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) ans_compress_kernel(
 {
   __shared__ __attribute__((aligned(16))) uint8_t lds[kWavesPerBlock][ans::kEncodeLds];
   const uint32_t w = wave::uniform(threadIdx.x >> 6);
-  const size_t chunk = (size_t)blockIdx.x * kWavesPerBlock + w;
-  if (chunk >= batch_size) {
-    return;
-  }
-  const uint8_t* src = wave::uniform_ptr((const uint8_t*)in_ptrs[chunk]);
-  uint8_t* dst = wave::uniform_ptr((uint8_t*)out_ptrs[chunk]);
-  const size_t n64 = wave::uniform64(in_bytes[chunk]);
-  /* a chunk larger than the caller declared would overrun the slot sized from GetMaxOutputChunkSize: refused (size 0) */
-  const uint32_t produced = n64 > max_chunk_bytes ? 0u : ans::encode_chunk(src, (uint32_t)n64, dst, lds[w]);
-  if (wave::lane_id() == 0) {
-    out_bytes[chunk] = produced;
-  }
+  lzl::compress_static<kWavesPerBlock>(in_ptrs, in_bytes, max_chunk_bytes, batch_size, out_ptrs, out_bytes,
+                                       [&](const uint8_t* src, uint32_t n, uint8_t* dst) -> uint32_t {
+                                         return ans::encode_chunk(src, n, dst, lds[w]);
+                                       });
 }
 
 __global__ void __launch_bounds__(64 * kWavesPerBlock) ans_decompress_kernel(
@@ -81,21 +75,14 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) ans_decompress_kernel(
 __global__ void __launch_bounds__(256) ans_decompress_size_kernel(
     const void* const* __restrict__ comp_ptrs, const size_t* __restrict__ comp_bytes, size_t* out_bytes, size_t batch_size)
 {
-  const size_t chunk = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (chunk >= batch_size) {
-    return;
-  }
-  const uint8_t* in = (const uint8_t*)comp_ptrs[chunk];
-  size_t n = 0;
-  if (comp_bytes[chunk] >= ans::kHeaderBytes && ans::load_as<uint32_t>(in) == ans::kMagic) {
-    n = ans::load_as<uint32_t>(in + 4);
-  }
-  out_bytes[chunk] = n;
+  lzl::size_by_lane(comp_ptrs, comp_bytes, out_bytes, batch_size, [](const uint8_t* in, size_t in_len) -> size_t {
+    return in_len >= ans::kHeaderBytes && ans::load_as<uint32_t>(in) == ans::kMagic ? ans::load_as<uint32_t>(in + 4) : 0;
+  });
 }
 
-bool opts_ok(nvcompBatchedANSOpts_t o)
+nvcompStatus_t opts_status(nvcompBatchedANSOpts_t o, size_t max_chunk_bytes)
 {
-  return o.type == nvcomp_rANS;
+  return lzl::compress_opts_status(o.type == nvcomp_rANS, max_chunk_bytes, nvcompANSCompressionMaxAllowedChunkSize);
 }
 
 } // namespace
@@ -105,27 +92,15 @@ extern "C" {
 nvcompStatus_t nvcompBatchedANSCompressGetTempSize(
     size_t /*batch_size*/, size_t max_uncompressed_chunk_bytes, nvcompBatchedANSOpts_t format_opts, size_t* temp_bytes)
 {
-  if (temp_bytes == nullptr || !opts_ok(format_opts)) {
-    return nvcompErrorInvalidValue;
-  }
-  if (max_uncompressed_chunk_bytes > nvcompANSCompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  *temp_bytes = 0; /* histogram and symbol table live in LDS */
-  return nvcompSuccess;
+  /* histogram and symbol table live in LDS */
+  return lzl::compress_query(temp_bytes, opts_status(format_opts, max_uncompressed_chunk_bytes), [] { return 0; });
 }
 
 nvcompStatus_t nvcompBatchedANSCompressGetMaxOutputChunkSize(
     size_t max_uncompressed_chunk_bytes, nvcompBatchedANSOpts_t format_opts, size_t* max_compressed_bytes)
 {
-  if (max_compressed_bytes == nullptr || !opts_ok(format_opts)) {
-    return nvcompErrorInvalidValue;
-  }
-  if (max_uncompressed_chunk_bytes > nvcompANSCompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  *max_compressed_bytes = ans::max_compressed_bytes(max_uncompressed_chunk_bytes);
-  return nvcompSuccess;
+  return lzl::compress_query(max_compressed_bytes, opts_status(format_opts, max_uncompressed_chunk_bytes),
+                             [&] { return ans::max_compressed_bytes(max_uncompressed_chunk_bytes); });
 }
 
 nvcompStatus_t nvcompBatchedANSCompressAsync(
@@ -142,34 +117,22 @@ nvcompStatus_t nvcompBatchedANSCompressAsync(
 {
   nvlog::call(3, "nvcompBatchedANSCompressAsync(batch_size=%zu, max_uncompressed_chunk_bytes=%zu, stream=%p)", batch_size,
               max_uncompressed_chunk_bytes, (void*)stream);
-  if (!opts_ok(format_opts)) {
-    return nvcompErrorInvalidValue;
+  const nvcompStatus_t st = opts_status(format_opts, max_uncompressed_chunk_bytes);
+  if (st != nvcompSuccess) {
+    return st;
   }
-  if (max_uncompressed_chunk_bytes > nvcompANSCompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_uncompressed_ptrs == nullptr || device_uncompressed_bytes == nullptr || device_compressed_ptrs == nullptr
-      || device_compressed_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  hipLaunchKernelGGL(ans_compress_kernel, dim3(grid_for(batch_size)), dim3(64 * kWavesPerBlock), 0, stream,
-                     device_uncompressed_ptrs, device_uncompressed_bytes, max_uncompressed_chunk_bytes, batch_size,
-                     device_compressed_ptrs, device_compressed_bytes);
-  return launch_status();
+  return lzl::checked_launch(
+      batch_size, lzl::all_set(device_uncompressed_ptrs, device_uncompressed_bytes, device_compressed_ptrs, device_compressed_bytes), [&] {
+        hipLaunchKernelGGL(ans_compress_kernel, dim3(grid_for(batch_size)), dim3(64 * kWavesPerBlock), 0, stream,
+                           device_uncompressed_ptrs, device_uncompressed_bytes, max_uncompressed_chunk_bytes, batch_size,
+                           device_compressed_ptrs, device_compressed_bytes);
+      });
 }
 
 nvcompStatus_t nvcompBatchedANSDecompressGetTempSize(
     size_t /*num_chunks*/, size_t /*max_uncompressed_chunk_bytes*/, size_t* temp_bytes)
 {
-  if (temp_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  *temp_bytes = 0; /* the decode table lives in LDS */
-  return nvcompSuccess;
+  return lzl::no_temp(temp_bytes); /* the decode table lives in LDS */
 }
 
 nvcompStatus_t nvcompBatchedANSDecompressAsync(
@@ -186,18 +149,12 @@ nvcompStatus_t nvcompBatchedANSDecompressAsync(
 {
   nvlog::call(3, "nvcompBatchedANSDecompressAsync(batch_size=%zu, statuses=%s, actual_sizes=%s, stream=%p)", batch_size,
               device_statuses ? "yes" : "null", device_actual_uncompressed_bytes ? "yes" : "null", (void*)stream);
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_compressed_ptrs == nullptr || device_compressed_bytes == nullptr || device_uncompressed_bytes == nullptr
-      || device_uncompressed_ptrs == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  hipLaunchKernelGGL(ans_decompress_kernel, dim3(grid_for(batch_size)), dim3(64 * kWavesPerBlock), 0, stream,
-                     device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
-                     device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, device_statuses);
-  return launch_status();
+  return lzl::checked_launch(
+      batch_size, lzl::all_set(device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes, device_uncompressed_ptrs), [&] {
+        hipLaunchKernelGGL(ans_decompress_kernel, dim3(grid_for(batch_size)), dim3(64 * kWavesPerBlock), 0, stream,
+                           device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
+                           device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, device_statuses);
+      });
 }
 
 nvcompStatus_t nvcompBatchedANSGetDecompressSizeAsync(
@@ -207,33 +164,11 @@ nvcompStatus_t nvcompBatchedANSGetDecompressSizeAsync(
     size_t batch_size,
     hipStream_t stream)
 {
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_compressed_ptrs == nullptr || device_compressed_bytes == nullptr || device_uncompressed_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  hipLaunchKernelGGL(ans_decompress_size_kernel, dim3((unsigned)((batch_size + 255) / 256)), dim3(256), 0, stream,
-                     device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes, batch_size);
-  return launch_status();
+  return lzl::size_by_lane_async<ans_decompress_size_kernel>(device_compressed_ptrs, device_compressed_bytes,
+                                                             device_uncompressed_bytes, batch_size, stream);
 }
 
-nvcompStatus_t nvcompBatchedANSCompressGetTempSizeEx(
-    size_t batch_size,
-    size_t max_uncompressed_chunk_bytes,
-    nvcompBatchedANSOpts_t format_opts,
-    size_t* temp_bytes,
-    const size_t /*max_total_uncompressed_bytes*/)
-{
-  /* the scratch does not depend on the batch's total size */
-  return nvcompBatchedANSCompressGetTempSize(batch_size, max_uncompressed_chunk_bytes, format_opts, temp_bytes);
-}
-
-nvcompStatus_t nvcompBatchedANSDecompressGetTempSizeEx(
-    size_t num_chunks, size_t max_uncompressed_chunk_bytes, size_t* temp_bytes, size_t /*max_total_uncompressed_bytes*/)
-{
-  return nvcompBatchedANSDecompressGetTempSize(num_chunks, max_uncompressed_chunk_bytes, temp_bytes);
-}
+NVCOMP_API_COMPRESS_TEMP_SIZE_EX(ANS, nvcompBatchedANSOpts_t)
+NVCOMP_API_DECOMPRESS_TEMP_SIZE_EX(ANS)
 
 } // extern "C"

@@ -1,20 +1,20 @@
 /*
  * api/bitcomp_api.hip -- C ABI of the batched Bitcomp codec (include/nvcomp/bitcomp.h) and
  * the kernels it launches: one wavefront per chunk, one launch per *Async call on the
- * caller's stream; nothing here allocates or synchronises.
+ * caller's stream; nothing here allocates or synchronises. The compress and size-query frames
+ * and the argument checks are common/api_batch.hip.h; the decode kernel spells its frame out,
+ * because the compiler writes it differently otherwise (profiles/api_frame_shared.md).
  */
 #include <hip/hip_runtime.h>
 
 #include "nvcomp/bitcomp.h"
 
-#include "common/api_launch.h"
+#include "common/api_batch.hip.h"
 #include "common/log.h"
 
 #include "bitcomp/bitcomp.hip.h"
 
 namespace {
-
-constexpr uint32_t kMaxOutCap = 1u << 26;
 
 /* Workgroups per CU the register allocation aims at: 8 (64 registers) spills 12-20 registers of the 8-byte element types,
  * whose values travel as two parts; 6 (85 registers) does not and is 5-24 % faster on them (round 3, 1 GiB: int64 key column
@@ -31,18 +31,10 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, sizeof(T) == 8 ? NVCOMP_B
     void* const* __restrict__ out_ptrs,
     size_t* out_bytes)
 {
-  const size_t chunk = (size_t)blockIdx.x * kWavesPerBlock + wave::uniform(threadIdx.x >> 6);
-  if (chunk >= batch_size) {
-    return;
-  }
-  const uint8_t* src = wave::uniform_ptr((const uint8_t*)in_ptrs[chunk]);
-  uint8_t* dst = wave::uniform_ptr((uint8_t*)out_ptrs[chunk]);
-  const size_t n64 = wave::uniform64(in_bytes[chunk]);
-  /* a chunk larger than the caller declared would overrun the slot sized from GetMaxOutputChunkSize: refused (size 0) */
-  const uint32_t produced = n64 > max_chunk_bytes ? 0u : bitcomp::encode_chunk<T, DELTA>(src, (uint32_t)n64, dst);
-  if (wave::lane_id() == 0) {
-    out_bytes[chunk] = produced;
-  }
+  lzl::compress_static<kWavesPerBlock>(in_ptrs, in_bytes, max_chunk_bytes, batch_size, out_ptrs, out_bytes,
+                                       [](const uint8_t* src, uint32_t n, uint8_t* dst) -> uint32_t {
+                                         return bitcomp::encode_chunk<T, DELTA>(src, n, dst);
+                                       });
 }
 
 template <bool CHECKED>
@@ -63,8 +55,8 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) bitcomp_decompress_kernel
   uint8_t* out = wave::uniform_ptr((uint8_t*)out_ptrs[chunk]);
   const size_t in_len64 = wave::uniform64(comp_bytes[chunk]);
   size_t cap64 = wave::uniform64(out_caps[chunk]);
-  if (cap64 > kMaxOutCap) {
-    cap64 = kMaxOutCap;
+  if (cap64 > lzl::kMaxOutCap) {
+    cap64 = lzl::kMaxOutCap;
   }
   uint32_t err = bitcomp::kErrNone;
   uint32_t produced = 0;
@@ -87,16 +79,9 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) bitcomp_decompress_kernel
 __global__ void __launch_bounds__(256) bitcomp_decompress_size_kernel(
     const void* const* __restrict__ comp_ptrs, const size_t* __restrict__ comp_bytes, size_t* out_bytes, size_t batch_size)
 {
-  const size_t chunk = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (chunk >= batch_size) {
-    return;
-  }
-  const uint8_t* in = (const uint8_t*)comp_ptrs[chunk];
-  size_t n = 0;
-  if (comp_bytes[chunk] >= bitcomp::kHeaderBytes && bitcomp::load_u32(in) == 0x01435442u) {
-    n = bitcomp::load_u32(in + 8);
-  }
-  out_bytes[chunk] = n;
+  lzl::size_by_lane(comp_ptrs, comp_bytes, out_bytes, batch_size, [](const uint8_t* in, size_t in_len) -> size_t {
+    return in_len >= bitcomp::kHeaderBytes && bitcomp::load_u32(in) == 0x01435442u ? bitcomp::load_u32(in + 8) : 0;
+  });
 }
 
 /* element size for a type code, 0 when the code is not a Bitcomp type */
@@ -115,9 +100,10 @@ unsigned elem_size(nvcompType_t t)
   }
 }
 
-bool opts_ok(nvcompBatchedBitcompFormatOpts o)
+nvcompStatus_t opts_status(nvcompBatchedBitcompFormatOpts o, size_t max_chunk_bytes)
 {
-  return (o.algorithm_type == 0 || o.algorithm_type == 1) && elem_size(o.data_type) != 0;
+  return lzl::compress_opts_status((o.algorithm_type == 0 || o.algorithm_type == 1) && elem_size(o.data_type) != 0, max_chunk_bytes,
+                                   nvcompBitcompCompressionMaxAllowedChunkSize);
 }
 
 } // namespace
@@ -127,28 +113,17 @@ extern "C" {
 nvcompStatus_t nvcompBatchedBitcompCompressGetTempSize(
     size_t /*batch_size*/, size_t max_uncompressed_chunk_bytes, nvcompBatchedBitcompFormatOpts format_opts, size_t* temp_bytes)
 {
-  if (temp_bytes == nullptr || !opts_ok(format_opts)) {
-    return nvcompErrorInvalidValue;
-  }
-  if (max_uncompressed_chunk_bytes > nvcompBitcompCompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  *temp_bytes = 0; /* a block's values stay in registers */
-  return nvcompSuccess;
+  /* a block's values stay in registers */
+  return lzl::compress_query(temp_bytes, opts_status(format_opts, max_uncompressed_chunk_bytes), [] { return 0; });
 }
 
 nvcompStatus_t nvcompBatchedBitcompCompressGetMaxOutputChunkSize(
     size_t max_uncompressed_chunk_bytes, nvcompBatchedBitcompFormatOpts format_opts, size_t* max_compressed_bytes)
 {
-  if (max_compressed_bytes == nullptr || !opts_ok(format_opts)) {
-    return nvcompErrorInvalidValue;
-  }
-  if (max_uncompressed_chunk_bytes > nvcompBitcompCompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  const size_t bound = bitcomp::max_compressed_bytes(max_uncompressed_chunk_bytes, elem_size(format_opts.data_type));
-  *max_compressed_bytes = (bound + 7) & ~(size_t)7; /* keeps consecutive output slots 8-byte aligned */
-  return nvcompSuccess;
+  return lzl::compress_query(max_compressed_bytes, opts_status(format_opts, max_uncompressed_chunk_bytes), [&] {
+    const size_t bound = bitcomp::max_compressed_bytes(max_uncompressed_chunk_bytes, elem_size(format_opts.data_type));
+    return (bound + 7) & ~(size_t)7; /* keeps consecutive output slots 8-byte aligned */
+  });
 }
 
 nvcompStatus_t nvcompBatchedBitcompCompressAsync(
@@ -165,69 +140,31 @@ nvcompStatus_t nvcompBatchedBitcompCompressAsync(
 {
   nvlog::call(3, "nvcompBatchedBitcompCompressAsync(batch_size=%zu, max_uncompressed_chunk_bytes=%zu, algo=%d, type=%d, stream=%p)",
               batch_size, max_uncompressed_chunk_bytes, format_opts.algorithm_type, (int)format_opts.data_type, (void*)stream);
-  if (!opts_ok(format_opts)) {
-    return nvcompErrorInvalidValue;
+  const nvcompStatus_t st = opts_status(format_opts, max_uncompressed_chunk_bytes);
+  if (st != nvcompSuccess) {
+    return st;
   }
-  if (max_uncompressed_chunk_bytes > nvcompBitcompCompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_uncompressed_ptrs == nullptr || device_uncompressed_bytes == nullptr || device_compressed_ptrs == nullptr
-      || device_compressed_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  const dim3 grid(grid_for(batch_size));
-  const dim3 block(64 * kWavesPerBlock);
-#define NVCOMP_BITCOMP_LAUNCH(T, D)                                                                            \
-  hipLaunchKernelGGL((bitcomp_compress_kernel<T, D>), grid, block, 0, stream, device_uncompressed_ptrs,        \
-                     device_uncompressed_bytes, max_uncompressed_chunk_bytes, batch_size, device_compressed_ptrs, \
-                     device_compressed_bytes)
-  const bool delta = format_opts.algorithm_type == 0;
-  switch (elem_size(format_opts.data_type)) {
-  case 1:
-    if (delta) {
-      NVCOMP_BITCOMP_LAUNCH(uint8_t, true);
-    } else {
-      NVCOMP_BITCOMP_LAUNCH(uint8_t, false);
-    }
-    break;
-  case 2:
-    if (delta) {
-      NVCOMP_BITCOMP_LAUNCH(uint16_t, true);
-    } else {
-      NVCOMP_BITCOMP_LAUNCH(uint16_t, false);
-    }
-    break;
-  case 4:
-    if (delta) {
-      NVCOMP_BITCOMP_LAUNCH(uint32_t, true);
-    } else {
-      NVCOMP_BITCOMP_LAUNCH(uint32_t, false);
-    }
-    break;
-  default:
-    if (delta) {
-      NVCOMP_BITCOMP_LAUNCH(uint64_t, true);
-    } else {
-      NVCOMP_BITCOMP_LAUNCH(uint64_t, false);
-    }
-    break;
-  }
-#undef NVCOMP_BITCOMP_LAUNCH
-  return launch_status();
+  return lzl::checked_launch(
+      batch_size, lzl::all_set(device_uncompressed_ptrs, device_uncompressed_bytes, device_compressed_ptrs, device_compressed_bytes), [&] {
+        const auto launch = [&](auto kernel_delta, auto kernel_plain) {
+          const auto kernel = format_opts.algorithm_type == 0 ? kernel_delta : kernel_plain;
+          hipLaunchKernelGGL(kernel, dim3(grid_for(batch_size)), dim3(64 * kWavesPerBlock), 0, stream, device_uncompressed_ptrs,
+                             device_uncompressed_bytes, max_uncompressed_chunk_bytes, batch_size, device_compressed_ptrs,
+                             device_compressed_bytes);
+        };
+        switch (elem_size(format_opts.data_type)) {
+        case 1: launch(bitcomp_compress_kernel<uint8_t, true>, bitcomp_compress_kernel<uint8_t, false>); break;
+        case 2: launch(bitcomp_compress_kernel<uint16_t, true>, bitcomp_compress_kernel<uint16_t, false>); break;
+        case 4: launch(bitcomp_compress_kernel<uint32_t, true>, bitcomp_compress_kernel<uint32_t, false>); break;
+        default: launch(bitcomp_compress_kernel<uint64_t, true>, bitcomp_compress_kernel<uint64_t, false>); break;
+        }
+      });
 }
 
 nvcompStatus_t nvcompBatchedBitcompDecompressGetTempSize(
     size_t /*num_chunks*/, size_t /*max_uncompressed_chunk_bytes*/, size_t* temp_bytes)
 {
-  if (temp_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  *temp_bytes = 0;
-  return nvcompSuccess;
+  return lzl::no_temp(temp_bytes);
 }
 
 nvcompStatus_t nvcompBatchedBitcompDecompressAsync(
@@ -244,26 +181,20 @@ nvcompStatus_t nvcompBatchedBitcompDecompressAsync(
 {
   nvlog::call(3, "nvcompBatchedBitcompDecompressAsync(batch_size=%zu, statuses=%s, actual_sizes=%s, stream=%p)", batch_size,
               device_statuses ? "yes" : "null", device_actual_uncompressed_bytes ? "yes" : "null", (void*)stream);
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_compressed_ptrs == nullptr || device_compressed_bytes == nullptr || device_uncompressed_bytes == nullptr
-      || device_uncompressed_ptrs == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
   const dim3 grid(grid_for(batch_size));
   const dim3 block(64 * kWavesPerBlock);
-  if (device_statuses != nullptr) {
-    hipLaunchKernelGGL((bitcomp_decompress_kernel<true>), grid, block, 0, stream, device_compressed_ptrs,
-                       device_compressed_bytes, device_uncompressed_bytes, device_actual_uncompressed_bytes, batch_size,
-                       device_uncompressed_ptrs, device_statuses);
-  } else {
-    hipLaunchKernelGGL((bitcomp_decompress_kernel<false>), grid, block, 0, stream, device_compressed_ptrs,
-                       device_compressed_bytes, device_uncompressed_bytes, device_actual_uncompressed_bytes, batch_size,
-                       device_uncompressed_ptrs, device_statuses);
-  }
-  return launch_status();
+  return lzl::checked_launch(
+      batch_size, lzl::all_set(device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes, device_uncompressed_ptrs), [&] {
+        if (device_statuses != nullptr) {
+          hipLaunchKernelGGL((bitcomp_decompress_kernel<true>), grid, block, 0, stream, device_compressed_ptrs,
+                             device_compressed_bytes, device_uncompressed_bytes, device_actual_uncompressed_bytes, batch_size,
+                             device_uncompressed_ptrs, device_statuses);
+        } else {
+          hipLaunchKernelGGL((bitcomp_decompress_kernel<false>), grid, block, 0, stream, device_compressed_ptrs,
+                             device_compressed_bytes, device_uncompressed_bytes, device_actual_uncompressed_bytes, batch_size,
+                             device_uncompressed_ptrs, device_statuses);
+        }
+      });
 }
 
 nvcompStatus_t nvcompBatchedBitcompGetDecompressSizeAsync(
@@ -273,33 +204,11 @@ nvcompStatus_t nvcompBatchedBitcompGetDecompressSizeAsync(
     size_t batch_size,
     hipStream_t stream)
 {
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_compressed_ptrs == nullptr || device_compressed_bytes == nullptr || device_uncompressed_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  hipLaunchKernelGGL(bitcomp_decompress_size_kernel, dim3((unsigned)((batch_size + 255) / 256)), dim3(256), 0, stream,
-                     device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes, batch_size);
-  return launch_status();
+  return lzl::size_by_lane_async<bitcomp_decompress_size_kernel>(device_compressed_ptrs, device_compressed_bytes,
+                                                                 device_uncompressed_bytes, batch_size, stream);
 }
 
-nvcompStatus_t nvcompBatchedBitcompCompressGetTempSizeEx(
-    size_t batch_size,
-    size_t max_uncompressed_chunk_bytes,
-    nvcompBatchedBitcompFormatOpts format_opts,
-    size_t* temp_bytes,
-    const size_t /*max_total_uncompressed_bytes*/)
-{
-  /* the scratch does not depend on the batch's total size */
-  return nvcompBatchedBitcompCompressGetTempSize(batch_size, max_uncompressed_chunk_bytes, format_opts, temp_bytes);
-}
-
-nvcompStatus_t nvcompBatchedBitcompDecompressGetTempSizeEx(
-    size_t num_chunks, size_t max_uncompressed_chunk_bytes, size_t* temp_bytes, size_t /*max_total_uncompressed_bytes*/)
-{
-  return nvcompBatchedBitcompDecompressGetTempSize(num_chunks, max_uncompressed_chunk_bytes, temp_bytes);
-}
+NVCOMP_API_COMPRESS_TEMP_SIZE_EX(Bitcomp, nvcompBatchedBitcompFormatOpts)
+NVCOMP_API_DECOMPRESS_TEMP_SIZE_EX(Bitcomp)
 
 } // extern "C"

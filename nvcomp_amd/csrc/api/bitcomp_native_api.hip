@@ -35,13 +35,12 @@
 #include "nvcomp/native/bitcomp.h"
 
 #include "common/log.h"
-#include "common/lz_launch.hip.h"
+#include "common/api_batch.hip.h"
 
 #include "bitcomp/quantize.hip.h"
 
 namespace {
 
-constexpr unsigned kWavesPerBlock = 4;
 constexpr uint32_t kSegLog2 = 16;
 constexpr size_t kSeg = (size_t)1 << kSegLog2; /* 64 KiB: the batched path's chunk, where its kernels were tuned */
 constexpr uint32_t kMagic = 0x014e4342u;       /* 'B' 'C' 'N' 1 */
@@ -287,12 +286,8 @@ Ops ops_for(uint32_t elem, int mode, bool delta)
   return elem == 1 ? ops_of<uint8_t, bitcomp::AsIs>(delta) : ops_fp<bitcomp::AsIs>(elem, delta);
 }
 
-void clear_stale_error()
-{
-  (void)hipGetLastError();
-}
-
-bitcompResult_t launch_status()
+/* launch_status() (common/api_launch.h) in this API's result type */
+bitcompResult_t native_launch_status()
 {
   return hipGetLastError() == hipSuccess ? BITCOMP_SUCCESS : BITCOMP_CUDA_KERNEL_LAUNCH_ERROR;
 }
@@ -448,7 +443,7 @@ bitcompResult_t compress(bitcompHandle_t h, const void* input, void* output, boo
   head.comp_bytes = 0;
   head.delta = lossy ? delta : 0.0;
   hipLaunchKernelGGL(native_header_kernel, dim3(1), dim3(64), 0, h->stream, out, head, h->segments);
-  return launch_status();
+  return native_launch_status();
 }
 
 } // namespace
@@ -555,7 +550,7 @@ bitcompResult_t bitcompPartialUncompress(
                                          : handle->grid_decompress);
   handle->ops.decompress(groups, handle->stream, (const uint8_t*)input, (uint8_t*)output, want, first, count, start_bytes,
                          length_bytes);
-  return launch_status();
+  return native_launch_status();
 }
 
 bitcompResult_t bitcompUncompress(const bitcompHandle_t handle, const void* input, void* output)
@@ -589,7 +584,7 @@ bitcompResult_t bitcompGetCompressedSizeAsync(const void* data, size_t* device_b
   }
   clear_stale_error();
   hipLaunchKernelGGL(native_size_kernel, dim3(1), dim3(64), 0, stream, (const uint8_t*)data, device_bytes);
-  return launch_status();
+  return native_launch_status();
 }
 
 bitcompResult_t bitcompGetUncompressedSize(const void* data, size_t* bytes)

@@ -5,12 +5,15 @@
  * Chunk container (little endian, 4-byte aligned; DESIGN.md "Cascaded stream layout"):
  *   u32 'CASC' | u8 type, num_RLEs, num_deltas, use_bp | u32 uncompressed bytes
  *   | u32 sub-chunk bytes | u32 num_sub | u32 sub_end[num_sub] | sub-chunk payloads
+ *
+ * The argument checks of the entry points are common/api_batch.hip.h; the decode and compress kernels have their own
+ * multi-pass shape.
  */
 #include <hip/hip_runtime.h>
 
 #include "nvcomp/cascaded.h"
 
-#include "common/api_launch.h"
+#include "common/api_batch.hip.h"
 #include "common/log.h"
 
 #include "cascaded/cascaded.hip.h"
@@ -449,6 +452,11 @@ __global__ void cascaded_size_kernel(
   sizes[i] = n;
 }
 
+nvcompStatus_t opts_status(const nvcompBatchedCascadedOpts_t& o, size_t max_chunk_bytes)
+{
+  return lzl::compress_opts_status(opts_ok(o), max_chunk_bytes, nvcompCascadedCompressionMaxAllowedChunkSize);
+}
+
 } // namespace
 
 extern "C" {
@@ -456,29 +464,18 @@ extern "C" {
 nvcompStatus_t nvcompBatchedCascadedCompressGetTempSize(
     size_t batch_size, size_t max_uncompressed_chunk_bytes, nvcompBatchedCascadedOpts_t format_opts, size_t* temp_bytes)
 {
-  if (temp_bytes == nullptr || !opts_ok(format_opts)) {
-    return nvcompErrorInvalidValue;
-  }
-  if (max_uncompressed_chunk_bytes > nvcompCascadedCompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  *temp_bytes = 4 * batch_size; /* one "repeat with a larger LDS slice" word per chunk */
-  return nvcompSuccess;
+  /* one "repeat with a larger LDS slice" word per chunk */
+  return lzl::compress_query(temp_bytes, opts_status(format_opts, max_uncompressed_chunk_bytes), [&] { return 4 * batch_size; });
 }
 
 nvcompStatus_t nvcompBatchedCascadedCompressGetMaxOutputChunkSize(
     size_t max_uncompressed_chunk_bytes, nvcompBatchedCascadedOpts_t format_opts, size_t* max_compressed_bytes)
 {
-  if (max_compressed_bytes == nullptr || !opts_ok(format_opts)) {
-    return nvcompErrorInvalidValue;
-  }
-  if (max_uncompressed_chunk_bytes > nvcompCascadedCompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  /* worst case: every sub-chunk stored raw (4-byte marker + bytes padded to 4) */
-  const size_t num_sub = (max_uncompressed_chunk_bytes + format_opts.chunk_size - 1) / format_opts.chunk_size;
-  *max_compressed_bytes = kHeaderBytes + 4 * num_sub + 8 * num_sub + ((max_uncompressed_chunk_bytes + 3) & ~(size_t)3);
-  return nvcompSuccess;
+  return lzl::compress_query(max_compressed_bytes, opts_status(format_opts, max_uncompressed_chunk_bytes), [&] {
+    /* worst case: every sub-chunk stored raw (4-byte marker + bytes padded to 4) */
+    const size_t num_sub = (max_uncompressed_chunk_bytes + format_opts.chunk_size - 1) / format_opts.chunk_size;
+    return kHeaderBytes + 4 * num_sub + 8 * num_sub + ((max_uncompressed_chunk_bytes + 3) & ~(size_t)3);
+  });
 }
 
 nvcompStatus_t nvcompBatchedCascadedCompressAsync(
@@ -495,73 +492,63 @@ nvcompStatus_t nvcompBatchedCascadedCompressAsync(
 {
   nvlog::call(3, "nvcompBatchedCascadedCompressAsync(batch_size=%zu, max_uncompressed_chunk_bytes=%zu, stream=%p)", batch_size,
               max_uncompressed_chunk_bytes, (void*)stream);
-  if (!opts_ok(format_opts)) {
-    return nvcompErrorInvalidValue;
+  const nvcompStatus_t st = opts_status(format_opts, max_uncompressed_chunk_bytes);
+  if (st != nvcompSuccess) {
+    return st;
   }
-  if (max_uncompressed_chunk_bytes > nvcompCascadedCompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_uncompressed_ptrs == nullptr || device_uncompressed_bytes == nullptr || device_compressed_ptrs == nullptr
-      || device_compressed_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  casc::Params p;
-  p.sub_bytes = (uint32_t)format_opts.chunk_size;
-  p.type = (uint32_t)format_opts.type;
-  p.num_rles = (uint32_t)format_opts.num_RLEs;
-  p.num_deltas = (uint32_t)format_opts.num_deltas;
-  p.use_bp = (uint32_t)format_opts.use_bp;
-  p.max_bytes = (uint32_t)max_uncompressed_chunk_bytes;
-  const uint32_t w = 1u << (p.type >> 1);
-  if (casc::decompress_lds_per_wave(p.sub_bytes, w, p.num_rles) + 64 > kBigBudget) { /* what the decoder may need */
-    return nvcompErrorNotSupported;
-  }
-  const uint32_t per_wave = (casc::compress_lds_per_wave(p.sub_bytes, w, p.num_rles) + 15u) & ~15u;
-  uint32_t waves = kBigBudget / per_wave;
-  waves = waves > 4 ? 4 : waves;
-  const unsigned grid = (unsigned)((batch_size + waves - 1) / waves);
-  clear_stale_error();
-  uint32_t* todo = (uint32_t*)device_temp_ptr;
-  if (todo == nullptr || temp_bytes < 4 * batch_size || per_wave <= kCompSmallBudget) {
-    /* no flag words (or nothing to gain): one launch sized for the worst case */
-    hipLaunchKernelGGL(cascaded_compress_kernel<false>, dim3(grid), dim3(64 * waves), per_wave * waves, stream,
+  const auto launch = [&]() -> nvcompStatus_t {
+    casc::Params p;
+    p.sub_bytes = (uint32_t)format_opts.chunk_size;
+    p.type = (uint32_t)format_opts.type;
+    p.num_rles = (uint32_t)format_opts.num_RLEs;
+    p.num_deltas = (uint32_t)format_opts.num_deltas;
+    p.use_bp = (uint32_t)format_opts.use_bp;
+    p.max_bytes = (uint32_t)max_uncompressed_chunk_bytes;
+    const uint32_t w = 1u << (p.type >> 1);
+    if (casc::decompress_lds_per_wave(p.sub_bytes, w, p.num_rles) + 64 > kBigBudget) { /* what the decoder may need */
+      return nvcompErrorNotSupported;
+    }
+    const uint32_t per_wave = (casc::compress_lds_per_wave(p.sub_bytes, w, p.num_rles) + 15u) & ~15u;
+    uint32_t waves = kBigBudget / per_wave;
+    waves = waves > 4 ? 4 : waves;
+    const unsigned grid = (unsigned)((batch_size + waves - 1) / waves);
+    uint32_t* todo = (uint32_t*)device_temp_ptr;
+    if (todo == nullptr || temp_bytes < 4 * batch_size || per_wave <= kCompSmallBudget) {
+      /* no flag words (or nothing to gain): one launch sized for the worst case */
+      hipLaunchKernelGGL(cascaded_compress_kernel<false>, dim3(grid), dim3(64 * waves), per_wave * waves, stream,
+                         device_uncompressed_ptrs, device_uncompressed_bytes, batch_size, device_compressed_ptrs,
+                         device_compressed_bytes, p, (uint32_t*)nullptr, 0u, 0u, per_wave, waves);
+      return nvcompSuccess;
+    }
+    /* pass 0: a small LDS slice at full occupancy; chunks whose streams overflow it are flagged and compressed again by
+     * the next pass; the last pass holds the worst case. The passes behind the first: the workgroups the card holds at their
+     * LDS size, looping (see the kernel) */
+    auto resident = [](size_t wgs, size_t lds_bytes) -> unsigned {
+      const size_t fit = kCus * (kLdsPerCu / lds_bytes);
+      return (unsigned)(wgs < fit ? wgs : fit);
+    };
+    const uint32_t last = per_wave > kMidBudget ? 2u : 1u;
+    hipLaunchKernelGGL(cascaded_compress_kernel<false>, dim3((unsigned)((batch_size + 3) / 4)), dim3(256), 4 * kCompSmallBudget, stream,
                        device_uncompressed_ptrs, device_uncompressed_bytes, batch_size, device_compressed_ptrs,
-                       device_compressed_bytes, p, (uint32_t*)nullptr, 0u, 0u, per_wave, waves);
-    return launch_status();
-  }
-  /* pass 0: a small LDS slice at full occupancy; chunks whose streams overflow it are flagged and compressed again by
-   * the next pass; the last pass holds the worst case. The passes behind the first: the workgroups the card holds at their
-   * LDS size, looping (see the kernel) */
-  auto resident = [](size_t wgs, size_t lds_bytes) -> unsigned {
-    const size_t fit = kCus * (kLdsPerCu / lds_bytes);
-    return (unsigned)(wgs < fit ? wgs : fit);
-  };
-  const uint32_t last = per_wave > kMidBudget ? 2u : 1u;
-  hipLaunchKernelGGL(cascaded_compress_kernel<false>, dim3((unsigned)((batch_size + 3) / 4)), dim3(256), 4 * kCompSmallBudget, stream,
-                     device_uncompressed_ptrs, device_uncompressed_bytes, batch_size, device_compressed_ptrs,
-                     device_compressed_bytes, p, todo, 0u, last, kCompSmallBudget, 4u);
-  if (last == 2) {
-    hipLaunchKernelGGL(cascaded_compress_kernel<true>, dim3(resident((batch_size + 3) / 4, 4 * kMidBudget)), dim3(256), 4 * kMidBudget,
+                       device_compressed_bytes, p, todo, 0u, last, kCompSmallBudget, 4u);
+    if (last == 2) {
+      hipLaunchKernelGGL(cascaded_compress_kernel<true>, dim3(resident((batch_size + 3) / 4, 4 * kMidBudget)), dim3(256), 4 * kMidBudget,
+                         stream, device_uncompressed_ptrs, device_uncompressed_bytes, batch_size, device_compressed_ptrs,
+                         device_compressed_bytes, p, todo, 1u, last, kMidBudget, 4u);
+    }
+    hipLaunchKernelGGL(cascaded_compress_kernel<true>, dim3(resident(grid, (size_t)per_wave * waves)), dim3(64 * waves), per_wave * waves,
                        stream, device_uncompressed_ptrs, device_uncompressed_bytes, batch_size, device_compressed_ptrs,
-                       device_compressed_bytes, p, todo, 1u, last, kMidBudget, 4u);
-  }
-  hipLaunchKernelGGL(cascaded_compress_kernel<true>, dim3(resident(grid, (size_t)per_wave * waves)), dim3(64 * waves), per_wave * waves,
-                     stream, device_uncompressed_ptrs, device_uncompressed_bytes, batch_size, device_compressed_ptrs,
-                     device_compressed_bytes, p, todo, last, last, per_wave, waves);
-  return launch_status();
+                       device_compressed_bytes, p, todo, last, last, per_wave, waves);
+    return nvcompSuccess;
+  };
+  return lzl::checked_launch(
+      batch_size, lzl::all_set(device_uncompressed_ptrs, device_uncompressed_bytes, device_compressed_ptrs, device_compressed_bytes), launch);
 }
 
 nvcompStatus_t nvcompBatchedCascadedDecompressGetTempSize(
     size_t num_chunks, size_t /*max_uncompressed_chunk_bytes*/, size_t* temp_bytes)
 {
-  if (temp_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  *temp_bytes = 4 * num_chunks; /* one "needs the large-LDS pass" word per chunk */
-  return nvcompSuccess;
+  return lzl::temp_size(num_chunks, temp_bytes, 4 * num_chunks); /* one "needs the large-LDS pass" word per chunk */
 }
 
 nvcompStatus_t nvcompBatchedCascadedDecompressAsync(
@@ -578,57 +565,53 @@ nvcompStatus_t nvcompBatchedCascadedDecompressAsync(
 {
   nvlog::call(3, "nvcompBatchedCascadedDecompressAsync(batch_size=%zu, statuses=%s, actual_sizes=%s, stream=%p)", batch_size,
               device_statuses ? "yes" : "null", device_actual_uncompressed_bytes ? "yes" : "null", (void*)stream);
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_compressed_ptrs == nullptr || device_compressed_bytes == nullptr || device_uncompressed_bytes == nullptr
-      || device_uncompressed_ptrs == nullptr || device_temp_ptr == nullptr || temp_bytes < 4 * batch_size) {
-    return nvcompErrorInvalidValue;
-  }
-  uint32_t* todo = (uint32_t*)device_temp_ptr;
-  clear_stale_error();
-  /* passes 1 and 2: the workgroups the card holds at 64 KiB of LDS each (two per CU), looping (see the kernel) */
-  const size_t kLaterGrid = kCus * (kLdsPerCu / kBigBudget);
-  if (batch_size <= kDecTeamMaxBatch) {
-    /* a workgroup per chunk, and the last pass folded into the one before it (decode_one_chunk: fold); batches the card
-     * holds at 64 KiB of LDS a workgroup start there: ONE launch */
-    const dim3 grid((unsigned)batch_size), later((unsigned)(batch_size < kLaterGrid ? batch_size : kLaterGrid));
-    const unsigned extra = 16; /* the team's verdict words, two pairs */
-    (void)extra;               /* (the host emulation's launch macro has no LDS size) */
-    if (batch_size <= kLaterGrid) {
-      hipLaunchKernelGGL((cascaded_decompress_kernel<true, false, true>), grid, dim3(256), 4 * kFastBudget + extra,
+  const bool arrays_ok = lzl::all_set(device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes, device_uncompressed_ptrs,
+                                      device_temp_ptr)
+                         && temp_bytes >= 4 * batch_size;
+  return lzl::checked_launch(batch_size, arrays_ok, [&] {
+    uint32_t* todo = (uint32_t*)device_temp_ptr;
+    /* passes 1 and 2: the workgroups the card holds at 64 KiB of LDS each (two per CU), looping (see the kernel) */
+    const size_t kLaterGrid = kCus * (kLdsPerCu / kBigBudget);
+    if (batch_size <= kDecTeamMaxBatch) {
+      /* a workgroup per chunk, and the last pass folded into the one before it (decode_one_chunk: fold); batches the card
+       * holds at 64 KiB of LDS a workgroup start there: ONE launch */
+      const dim3 grid((unsigned)batch_size), later((unsigned)(batch_size < kLaterGrid ? batch_size : kLaterGrid));
+      const unsigned extra = 16; /* the team's verdict words, two pairs */
+      (void)extra;               /* (the host emulation's launch macro has no LDS size) */
+      if (batch_size <= kLaterGrid) {
+        hipLaunchKernelGGL((cascaded_decompress_kernel<true, false, true>), grid, dim3(256), 4 * kFastBudget + extra,
+                           stream, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
+                           device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, device_statuses, todo, 1u,
+                           kFastBudget, 4u);
+        return;
+      }
+      hipLaunchKernelGGL((cascaded_decompress_kernel<true, false>), grid, dim3(256), 4 * kDecSmallBudget + extra,
+                         stream, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
+                         device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, device_statuses, todo, 0u,
+                         kDecSmallBudget, 4u);
+      hipLaunchKernelGGL((cascaded_decompress_kernel<true, true, true>), later, dim3(256), 4 * kFastBudget + extra,
                          stream, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
                          device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, device_statuses, todo, 1u,
                          kFastBudget, 4u);
-      return launch_status();
+      return;
+    } else {
+      const size_t wgs = (batch_size + 3) / 4;
+      const dim3 grid((unsigned)wgs), later((unsigned)(wgs < kLaterGrid ? wgs : kLaterGrid));
+      /* (four waves a workgroup: one and two measured the same, profiles/r06_ab_cascaded_launches.jsonl r6cascw) */
+      hipLaunchKernelGGL((cascaded_decompress_kernel<false, false>), grid, dim3(256), 4 * kDecSmallBudget,
+                         stream, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
+                         device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, device_statuses, todo, 0u,
+                         kDecSmallBudget, 4u);
+      hipLaunchKernelGGL((cascaded_decompress_kernel<false, true>), later, dim3(256), 4 * kFastBudget,
+                         stream, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
+                         device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, device_statuses, todo, 1u,
+                         kFastBudget, 4u);
     }
-    hipLaunchKernelGGL((cascaded_decompress_kernel<true, false>), grid, dim3(256), 4 * kDecSmallBudget + extra,
-                       stream, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
-                       device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, device_statuses, todo, 0u,
-                       kDecSmallBudget, 4u);
-    hipLaunchKernelGGL((cascaded_decompress_kernel<true, true, true>), later, dim3(256), 4 * kFastBudget + extra,
-                       stream, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
-                       device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, device_statuses, todo, 1u,
-                       kFastBudget, 4u);
-    return launch_status();
-  } else {
-    const size_t wgs = (batch_size + 3) / 4;
-    const dim3 grid((unsigned)wgs), later((unsigned)(wgs < kLaterGrid ? wgs : kLaterGrid));
-    /* (four waves a workgroup: one and two measured the same, profiles/r06_ab_cascaded_launches.jsonl r6cascw) */
-    hipLaunchKernelGGL((cascaded_decompress_kernel<false, false>), grid, dim3(256), 4 * kDecSmallBudget,
-                       stream, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
-                       device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, device_statuses, todo, 0u,
-                       kDecSmallBudget, 4u);
-    hipLaunchKernelGGL((cascaded_decompress_kernel<false, true>), later, dim3(256), 4 * kFastBudget,
-                       stream, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
-                       device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, device_statuses, todo, 1u,
-                       kFastBudget, 4u);
-  }
-  hipLaunchKernelGGL((cascaded_decompress_kernel<false, true>), dim3((unsigned)(batch_size < kLaterGrid ? batch_size : kLaterGrid)),
-                     dim3(64), kBigBudget, stream, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
-                     device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, device_statuses, todo, 2u,
-                     kBigBudget, 1u);
-  return launch_status();
+    hipLaunchKernelGGL((cascaded_decompress_kernel<false, true>), dim3((unsigned)(batch_size < kLaterGrid ? batch_size : kLaterGrid)),
+                       dim3(64), kBigBudget, stream, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
+                       device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, device_statuses, todo, 2u,
+                       kBigBudget, 1u);
+  });
 }
 
 nvcompStatus_t nvcompBatchedCascadedGetDecompressSizeAsync(
@@ -638,34 +621,12 @@ nvcompStatus_t nvcompBatchedCascadedGetDecompressSizeAsync(
     size_t batch_size,
     hipStream_t stream)
 {
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_compressed_ptrs == nullptr || device_compressed_bytes == nullptr || device_uncompressed_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  hipLaunchKernelGGL(cascaded_size_kernel, dim3((unsigned)((batch_size + 255) / 256)), dim3(256), 0, stream,
-                     device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes, batch_size);
-  return launch_status();
+  return lzl::size_by_lane_async<cascaded_size_kernel>(device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
+                                                       batch_size, stream);
 }
 
-nvcompStatus_t nvcompBatchedCascadedCompressGetTempSizeEx(
-    size_t batch_size,
-    size_t max_uncompressed_chunk_bytes,
-    nvcompBatchedCascadedOpts_t format_opts,
-    size_t* temp_bytes,
-    const size_t /*max_total_uncompressed_bytes*/)
-{
-  /* the scratch does not depend on the batch's total size */
-  return nvcompBatchedCascadedCompressGetTempSize(batch_size, max_uncompressed_chunk_bytes, format_opts, temp_bytes);
-}
-
-nvcompStatus_t nvcompBatchedCascadedDecompressGetTempSizeEx(
-    size_t num_chunks, size_t max_uncompressed_chunk_bytes, size_t* temp_bytes, size_t /*max_total_uncompressed_bytes*/)
-{
-  return nvcompBatchedCascadedDecompressGetTempSize(num_chunks, max_uncompressed_chunk_bytes, temp_bytes);
-}
+NVCOMP_API_COMPRESS_TEMP_SIZE_EX(Cascaded, nvcompBatchedCascadedOpts_t)
+NVCOMP_API_DECOMPRESS_TEMP_SIZE_EX(Cascaded)
 
 } // extern "C"
 

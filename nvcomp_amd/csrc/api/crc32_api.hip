@@ -17,9 +17,8 @@
 
 #include "nvcomp/crc32.h"
 
-#include "common/api_launch.h"
+#include "common/api_batch.hip.h"
 #include "common/log.h"
-#include "common/lz_launch.hip.h"
 #include "common/wave.h"
 
 #include "hlif/crc32.hip.h"

@@ -1,7 +1,9 @@
 /*
  * api/deflate_api.hip -- C ABI of the batched DEFLATE and gzip codecs (include/nvcomp/deflate.h, include/nvcomp/gzip.h)
  * and the kernels it launches. Host side does argument checks and one launch per *Async call on the caller's
- * stream; nothing here allocates or synchronises.
+ * stream; nothing here allocates or synchronises. The argument checks and gzip's size-query frame are
+ * common/api_batch.hip.h; the other kernels spell their frames out, because the compiler writes them differently otherwise
+ * (profiles/api_frame_shared.md).
  */
 #include <hip/hip_runtime.h>
 
@@ -10,7 +12,7 @@
 #include "nvcomp/deflate.h"
 #include "nvcomp/gzip.h"
 
-#include "common/api_launch.h"
+#include "common/api_batch.hip.h"
 #include "common/log.h"
 
 #include "deflate/deflate_decode.hip.h"
@@ -27,7 +29,6 @@ namespace {
 constexpr unsigned kDecWaves = NVCOMP_DEFLATE_WAVES_PER_BLOCK;
 constexpr unsigned kDecWavesPerSimd = deflate::kLdsPerWave <= 8192 ? 5 : deflate::kLdsPerWave <= 10240 ? 4 : 3;
 constexpr unsigned kEncWaves = 2; /* 10 / 11.3 KiB of LDS per wave: 16 / 14 waves per CU in workgroups of two */
-constexpr uint32_t kMaxOutCap = 1u << 26;
 
 /* The bounds and match-offset checks always run: DEFLATE / gzip streams come from outside (CPU producers, files), and a
  * corrupt one must never write outside its output slot or read in front of it -- whether or not the caller asked for
@@ -52,8 +53,8 @@ __global__ void __launch_bounds__(64 * kDecWaves, kDecWavesPerSimd) deflate_deco
   uint8_t* out = wave::uniform_ptr((uint8_t*)out_ptrs[chunk]);
   const size_t in_len64 = wave::uniform64(comp_bytes[chunk]);
   size_t cap64 = wave::uniform64(out_caps[chunk]);
-  if (cap64 > kMaxOutCap) {
-    cap64 = kMaxOutCap;
+  if (cap64 > lzl::kMaxOutCap) {
+    cap64 = lzl::kMaxOutCap;
   }
   uint32_t err = lz::kErrNone;
   uint32_t produced = 0;
@@ -104,17 +105,12 @@ __global__ void __launch_bounds__(64 * kDecWaves, kDecWavesPerSimd) deflate_size
 __global__ void __launch_bounds__(256) gzip_size_kernel(
     const void* const* __restrict__ comp_ptrs, const size_t* __restrict__ comp_bytes, size_t* uncompressed_bytes, size_t batch_size)
 {
-  const size_t chunk = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (chunk >= batch_size) {
-    return;
-  }
-  const uint8_t* in = (const uint8_t*)comp_ptrs[chunk];
-  const size_t n = comp_bytes[chunk];
-  size_t size = 0;
-  if (n >= 18 && in[0] == 0x1f && in[1] == 0x8b && in[2] == 8) {
-    size = (size_t)in[n - 4] | ((size_t)in[n - 3] << 8) | ((size_t)in[n - 2] << 16) | ((size_t)in[n - 1] << 24);
-  }
-  uncompressed_bytes[chunk] = size;
+  lzl::size_by_lane(comp_ptrs, comp_bytes, uncompressed_bytes, batch_size, [](const uint8_t* in, size_t n) -> size_t {
+    if (n >= 18 && in[0] == 0x1f && in[1] == 0x8b && in[2] == 8) {
+      return (size_t)in[n - 4] | ((size_t)in[n - 3] << 8) | ((size_t)in[n - 2] << 16) | ((size_t)in[n - 1] << 24);
+    }
+    return 0;
+  });
 }
 
 /* DYNAMIC: per-chunk Huffman codes (nvcompBatchedDeflateOpts_t.algo >= 1: two runs of the match finder and a code
@@ -147,9 +143,9 @@ __global__ void __launch_bounds__(64 * kEncWaves, DYNAMIC ? 3 : 4) deflate_compr
   }
 }
 
-bool deflate_opts_ok(nvcompBatchedDeflateOpts_t opts)
+nvcompStatus_t opts_status(nvcompBatchedDeflateOpts_t opts, size_t max_chunk_bytes)
 {
-  return opts.algo >= 0 && opts.algo <= 2;
+  return lzl::compress_opts_status(opts.algo >= 0 && opts.algo <= 2, max_chunk_bytes, nvcompDeflateCompressionMaxAllowedChunkSize);
 }
 
 template <uint32_t FLAGS>
@@ -166,20 +162,14 @@ nvcompStatus_t decompress_async(
 {
   nvlog::call(3, "%s(batch_size=%zu, statuses=%s, actual_sizes=%s, stream=%p)", name, batch_size,
               device_statuses ? "yes" : "null", device_actual_uncompressed_bytes ? "yes" : "null", (void*)stream);
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_compressed_ptrs == nullptr || device_compressed_bytes == nullptr || device_uncompressed_bytes == nullptr
-      || device_uncompressed_ptrs == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  const dim3 grid((unsigned)((batch_size + kDecWaves - 1) / kDecWaves));
-  const dim3 block(64 * kDecWaves);
-  hipLaunchKernelGGL((deflate_decompress_kernel<FLAGS>), grid, block, 0, stream, device_compressed_ptrs,
-                     device_compressed_bytes, device_uncompressed_bytes, device_actual_uncompressed_bytes, batch_size,
-                     device_uncompressed_ptrs, device_statuses);
-  return launch_status();
+  return lzl::checked_launch(
+      batch_size, lzl::all_set(device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes, device_uncompressed_ptrs), [&] {
+        const dim3 grid((unsigned)((batch_size + kDecWaves - 1) / kDecWaves));
+        const dim3 block(64 * kDecWaves);
+        hipLaunchKernelGGL((deflate_decompress_kernel<FLAGS>), grid, block, 0, stream, device_compressed_ptrs,
+                           device_compressed_bytes, device_uncompressed_bytes, device_actual_uncompressed_bytes, batch_size,
+                           device_uncompressed_ptrs, device_statuses);
+      });
 }
 
 } // namespace
@@ -189,18 +179,10 @@ extern "C" {
 nvcompStatus_t nvcompBatchedDeflateDecompressGetTempSize(
     size_t /*num_chunks*/, size_t /*max_uncompressed_chunk_bytes*/, size_t* temp_bytes)
 {
-  if (temp_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  *temp_bytes = 0; /* tables, rings and window live in LDS */
-  return nvcompSuccess;
+  return lzl::no_temp(temp_bytes); /* tables, rings and window live in LDS */
 }
 
-nvcompStatus_t nvcompBatchedDeflateDecompressGetTempSizeEx(
-    size_t num_chunks, size_t max_uncompressed_chunk_bytes, size_t* temp_bytes, size_t /*max_total_uncompressed_bytes*/)
-{
-  return nvcompBatchedDeflateDecompressGetTempSize(num_chunks, max_uncompressed_chunk_bytes, temp_bytes);
-}
+NVCOMP_API_DECOMPRESS_TEMP_SIZE_EX(Deflate)
 
 nvcompStatus_t nvcompBatchedDeflateDecompressAsync(
     const void* const* device_compressed_ptrs,
@@ -226,16 +208,8 @@ nvcompStatus_t nvcompBatchedDeflateGetDecompressSizeAsync(
     size_t batch_size,
     hipStream_t stream)
 {
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_compressed_ptrs == nullptr || device_compressed_bytes == nullptr || device_uncompressed_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  hipLaunchKernelGGL(deflate_size_kernel, dim3((unsigned)((batch_size + kDecWaves - 1) / kDecWaves)), dim3(64 * kDecWaves), 0,
-                     stream, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes, batch_size);
-  return launch_status();
+  return lzl::decompress_size_async<deflate_size_kernel>(device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
+                                                         batch_size, stream, kDecWaves, 64 * kDecWaves);
 }
 
 nvcompStatus_t nvcompBatchedGzipDecompressGetTempSize(
@@ -244,11 +218,7 @@ nvcompStatus_t nvcompBatchedGzipDecompressGetTempSize(
   return nvcompBatchedDeflateDecompressGetTempSize(num_chunks, max_uncompressed_chunk_bytes, temp_bytes);
 }
 
-nvcompStatus_t nvcompBatchedGzipDecompressGetTempSizeEx(
-    size_t num_chunks, size_t max_uncompressed_chunk_bytes, size_t* temp_bytes, size_t /*max_total_uncompressed_bytes*/)
-{
-  return nvcompBatchedDeflateDecompressGetTempSize(num_chunks, max_uncompressed_chunk_bytes, temp_bytes);
-}
+NVCOMP_API_DECOMPRESS_TEMP_SIZE_EX(Gzip)
 
 nvcompStatus_t nvcompBatchedGzipDecompressAsync(
     const void* const* device_compressed_ptrs,
@@ -274,52 +244,24 @@ nvcompStatus_t nvcompBatchedGzipGetDecompressSizeAsync(
     size_t batch_size,
     hipStream_t stream)
 {
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_compressed_ptrs == nullptr || device_compressed_bytes == nullptr || device_uncompressed_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  hipLaunchKernelGGL(gzip_size_kernel, dim3((unsigned)((batch_size + 255) / 256)), dim3(256), 0, stream,
-                     device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes, batch_size);
-  return launch_status();
+  return lzl::size_by_lane_async<gzip_size_kernel>(device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
+                                                   batch_size, stream);
 }
 
 nvcompStatus_t nvcompBatchedDeflateCompressGetTempSize(
     size_t /*batch_size*/, size_t max_uncompressed_chunk_bytes, nvcompBatchedDeflateOpts_t format_opts, size_t* temp_bytes)
 {
-  if (temp_bytes == nullptr || !deflate_opts_ok(format_opts)) {
-    return nvcompErrorInvalidValue;
-  }
-  if (max_uncompressed_chunk_bytes > nvcompDeflateCompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  *temp_bytes = 0; /* hash table, input image and bit staging live in LDS */
-  return nvcompSuccess;
+  /* hash table, input image and bit staging live in LDS */
+  return lzl::compress_query(temp_bytes, opts_status(format_opts, max_uncompressed_chunk_bytes), [] { return 0; });
 }
 
-nvcompStatus_t nvcompBatchedDeflateCompressGetTempSizeEx(
-    size_t batch_size,
-    size_t max_uncompressed_chunk_bytes,
-    nvcompBatchedDeflateOpts_t format_opts,
-    size_t* temp_bytes,
-    const size_t /*max_total_uncompressed_bytes*/)
-{
-  return nvcompBatchedDeflateCompressGetTempSize(batch_size, max_uncompressed_chunk_bytes, format_opts, temp_bytes);
-}
+NVCOMP_API_COMPRESS_TEMP_SIZE_EX(Deflate, nvcompBatchedDeflateOpts_t)
 
 nvcompStatus_t nvcompBatchedDeflateCompressGetMaxOutputChunkSize(
     size_t max_uncompressed_chunk_bytes, nvcompBatchedDeflateOpts_t format_opts, size_t* max_compressed_bytes)
 {
-  if (max_compressed_bytes == nullptr || !deflate_opts_ok(format_opts)) {
-    return nvcompErrorInvalidValue;
-  }
-  if (max_uncompressed_chunk_bytes > nvcompDeflateCompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  *max_compressed_bytes = deflate::max_compressed_size(max_uncompressed_chunk_bytes);
-  return nvcompSuccess;
+  return lzl::compress_query(max_compressed_bytes, opts_status(format_opts, max_uncompressed_chunk_bytes),
+                             [&] { return deflate::max_compressed_size(max_uncompressed_chunk_bytes); });
 }
 
 nvcompStatus_t nvcompBatchedDeflateCompressAsync(
@@ -336,29 +278,17 @@ nvcompStatus_t nvcompBatchedDeflateCompressAsync(
 {
   nvlog::call(3, "nvcompBatchedDeflateCompressAsync(batch_size=%zu, max_uncompressed_chunk_bytes=%zu, stream=%p)", batch_size,
               max_uncompressed_chunk_bytes, (void*)stream);
-  if (!deflate_opts_ok(format_opts)) {
-    return nvcompErrorInvalidValue;
+  const nvcompStatus_t st = opts_status(format_opts, max_uncompressed_chunk_bytes);
+  if (st != nvcompSuccess) {
+    return st;
   }
-  if (max_uncompressed_chunk_bytes > nvcompDeflateCompressionMaxAllowedChunkSize) {
-    return nvcompErrorChunkSizeTooLarge;
-  }
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_uncompressed_ptrs == nullptr || device_uncompressed_bytes == nullptr || device_compressed_ptrs == nullptr
-      || device_compressed_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  const dim3 grid((unsigned)((batch_size + kEncWaves - 1) / kEncWaves)), block(64 * kEncWaves);
-  if (format_opts.algo == 0) {
-    hipLaunchKernelGGL(deflate_compress_kernel<false>, grid, block, 0, stream, device_uncompressed_ptrs, device_uncompressed_bytes,
-                       max_uncompressed_chunk_bytes, batch_size, device_compressed_ptrs, device_compressed_bytes);
-  } else {
-    hipLaunchKernelGGL(deflate_compress_kernel<true>, grid, block, 0, stream, device_uncompressed_ptrs, device_uncompressed_bytes,
-                       max_uncompressed_chunk_bytes, batch_size, device_compressed_ptrs, device_compressed_bytes);
-  }
-  return launch_status();
+  return lzl::checked_launch(
+      batch_size, lzl::all_set(device_uncompressed_ptrs, device_uncompressed_bytes, device_compressed_ptrs, device_compressed_bytes), [&] {
+        const dim3 grid((unsigned)((batch_size + kEncWaves - 1) / kEncWaves)), block(64 * kEncWaves);
+        const auto kernel = format_opts.algo == 0 ? deflate_compress_kernel<false> : deflate_compress_kernel<true>;
+        hipLaunchKernelGGL(kernel, grid, block, 0, stream, device_uncompressed_ptrs, device_uncompressed_bytes,
+                           max_uncompressed_chunk_bytes, batch_size, device_compressed_ptrs, device_compressed_bytes);
+      });
 }
 
 } // extern "C"

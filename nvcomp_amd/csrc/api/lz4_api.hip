@@ -2,7 +2,7 @@
  * api/lz4_api.hip -- C ABI of the batched LZ4 codec (include/nvcomp/lz4.h) and
  * the kernels it launches. Host side does argument checks and one launch per
  * *Async call on the caller's stream; nothing here allocates or synchronises.
- * What LZ4 shares with Snappy (kernel bodies, launches, dispatch) is common/lz_api.hip.h.
+ * What LZ4 shares with Snappy (kernel bodies, dispatch) is common/lz_api.hip.h, what with every format common/api_batch.hip.h.
  */
 #include <hip/hip_runtime.h>
 
@@ -192,11 +192,7 @@ nvcompStatus_t nvcompBatchedLZ4DecompressGetTempSize(
                         num_chunks > lzl::kPairMaxBatch && NVCOMP_LZ_INDEX ? lzl::index_temp_bytes(num_chunks) : lzl::kTicketBytes);
 }
 
-nvcompStatus_t nvcompBatchedLZ4DecompressGetTempSizeEx(
-    size_t num_chunks, size_t max_uncompressed_chunk_bytes, size_t* temp_bytes, size_t /*max_total_uncompressed_bytes*/)
-{
-  return nvcompBatchedLZ4DecompressGetTempSize(num_chunks, max_uncompressed_chunk_bytes, temp_bytes);
-}
+NVCOMP_API_DECOMPRESS_TEMP_SIZE_EX(LZ4)
 
 nvcompStatus_t nvcompBatchedLZ4DecompressAsync(
     const void* const* device_compressed_ptrs,
@@ -224,16 +220,10 @@ nvcompStatus_t nvcompAmdBatchedLZ4TokenIndexAsync(
     unsigned* device_info,
     hipStream_t stream)
 {
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_compressed_ptrs == nullptr || device_compressed_bytes == nullptr || device_lists == nullptr || device_info == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  hipLaunchKernelGGL(lz4_token_index_kernel, dim3((unsigned)batch_size), dim3(64), 0, stream, device_compressed_ptrs,
-                     device_compressed_bytes, batch_size, (uint16_t*)device_lists, (uint32_t*)device_info);
-  return launch_status();
+  return lzl::checked_launch(batch_size, lzl::all_set(device_compressed_ptrs, device_compressed_bytes, device_lists, device_info), [&] {
+    hipLaunchKernelGGL(lz4_token_index_kernel, dim3((unsigned)batch_size), dim3(64), 0, stream, device_compressed_ptrs,
+                       device_compressed_bytes, batch_size, (uint16_t*)device_lists, (uint32_t*)device_info);
+  });
 }
 
 nvcompStatus_t nvcompBatchedLZ4GetDecompressSizeAsync(
@@ -250,29 +240,17 @@ nvcompStatus_t nvcompBatchedLZ4GetDecompressSizeAsync(
 nvcompStatus_t nvcompBatchedLZ4CompressGetTempSize(
     size_t batch_size, size_t max_uncompressed_chunk_bytes, nvcompBatchedLZ4Opts_t format_opts, size_t* temp_bytes)
 {
-  const nvcompStatus_t st = temp_bytes == nullptr ? nvcompErrorInvalidValue : lz4_opts_status(format_opts, max_uncompressed_chunk_bytes);
-  return st != nvcompSuccess ? st : lzl::temp_size(batch_size, temp_bytes);
+  return lzl::compress_query(temp_bytes, lz4_opts_status(format_opts, max_uncompressed_chunk_bytes),
+                             [&] { return batch_size == 0 ? 0 : lzl::kTicketBytes; });
 }
 
-nvcompStatus_t nvcompBatchedLZ4CompressGetTempSizeEx(
-    size_t batch_size,
-    size_t max_uncompressed_chunk_bytes,
-    nvcompBatchedLZ4Opts_t format_opts,
-    size_t* temp_bytes,
-    const size_t /*max_total_uncompressed_bytes*/)
-{
-  return nvcompBatchedLZ4CompressGetTempSize(batch_size, max_uncompressed_chunk_bytes, format_opts, temp_bytes);
-}
+NVCOMP_API_COMPRESS_TEMP_SIZE_EX(LZ4, nvcompBatchedLZ4Opts_t)
 
 nvcompStatus_t nvcompBatchedLZ4CompressGetMaxOutputChunkSize(
     size_t max_uncompressed_chunk_bytes, nvcompBatchedLZ4Opts_t format_opts, size_t* max_compressed_bytes)
 {
-  const nvcompStatus_t st =
-      max_compressed_bytes == nullptr ? nvcompErrorInvalidValue : lz4_opts_status(format_opts, max_uncompressed_chunk_bytes);
-  if (st == nvcompSuccess) {
-    *max_compressed_bytes = lz4_bound(max_uncompressed_chunk_bytes);
-  }
-  return st;
+  return lzl::compress_query(max_compressed_bytes, lz4_opts_status(format_opts, max_uncompressed_chunk_bytes),
+                             [&] { return lz4_bound(max_uncompressed_chunk_bytes); });
 }
 
 nvcompStatus_t nvcompBatchedLZ4CompressAsync(

@@ -2,7 +2,7 @@
  * api/snappy_api.hip -- C ABI of the batched Snappy codec (include/nvcomp/snappy.h) and
  * the kernels it launches. Host side does argument checks and one launch per
  * *Async call on the caller's stream; nothing here allocates or synchronises.
- * What Snappy shares with LZ4 (kernel bodies, launches, dispatch) is common/lz_api.hip.h.
+ * What Snappy shares with LZ4 (kernel bodies, dispatch) is common/lz_api.hip.h, what with every format common/api_batch.hip.h.
  */
 #include <hip/hip_runtime.h>
 
@@ -127,11 +127,7 @@ nvcompStatus_t nvcompBatchedSnappyDecompressGetTempSize(
   return lzl::temp_size(num_chunks, temp_bytes);
 }
 
-nvcompStatus_t nvcompBatchedSnappyDecompressGetTempSizeEx(
-    size_t num_chunks, size_t max_uncompressed_chunk_bytes, size_t* temp_bytes, size_t /*max_total_uncompressed_bytes*/)
-{
-  return nvcompBatchedSnappyDecompressGetTempSize(num_chunks, max_uncompressed_chunk_bytes, temp_bytes);
-}
+NVCOMP_API_DECOMPRESS_TEMP_SIZE_EX(Snappy)
 
 nvcompStatus_t nvcompBatchedSnappyDecompressAsync(
     const void* const* device_compressed_ptrs,
@@ -165,30 +161,18 @@ nvcompStatus_t nvcompBatchedSnappyGetDecompressSizeAsync(
 nvcompStatus_t nvcompBatchedSnappyCompressGetTempSize(
     size_t batch_size, size_t max_uncompressed_chunk_bytes, nvcompBatchedSnappyOpts_t format_opts, size_t* temp_bytes)
 {
-  const nvcompStatus_t st = temp_bytes == nullptr ? nvcompErrorInvalidValue : snappy_opts_status(format_opts, max_uncompressed_chunk_bytes);
-  return st != nvcompSuccess ? st : lzl::temp_size(batch_size, temp_bytes);
+  return lzl::compress_query(temp_bytes, snappy_opts_status(format_opts, max_uncompressed_chunk_bytes),
+                             [&] { return batch_size == 0 ? 0 : lzl::kTicketBytes; });
 }
 
-nvcompStatus_t nvcompBatchedSnappyCompressGetTempSizeEx(
-    size_t batch_size,
-    size_t max_uncompressed_chunk_bytes,
-    nvcompBatchedSnappyOpts_t format_opts,
-    size_t* temp_bytes,
-    const size_t /*max_total_uncompressed_bytes*/)
-{
-  return nvcompBatchedSnappyCompressGetTempSize(batch_size, max_uncompressed_chunk_bytes, format_opts, temp_bytes);
-}
+NVCOMP_API_COMPRESS_TEMP_SIZE_EX(Snappy, nvcompBatchedSnappyOpts_t)
 
 nvcompStatus_t nvcompBatchedSnappyCompressGetMaxOutputChunkSize(
     size_t max_uncompressed_chunk_bytes, nvcompBatchedSnappyOpts_t format_opts, size_t* max_compressed_bytes)
 {
-  const nvcompStatus_t st =
-      max_compressed_bytes == nullptr ? nvcompErrorInvalidValue : snappy_opts_status(format_opts, max_uncompressed_chunk_bytes);
-  if (st == nvcompSuccess) {
-    /* the raw format's classic bound: preamble + literal headers */
-    *max_compressed_bytes = 32 + max_uncompressed_chunk_bytes + max_uncompressed_chunk_bytes / 6;
-  }
-  return st;
+  /* the raw format's classic bound: preamble + literal headers */
+  return lzl::compress_query(max_compressed_bytes, snappy_opts_status(format_opts, max_uncompressed_chunk_bytes),
+                             [&] { return 32 + max_uncompressed_chunk_bytes + max_uncompressed_chunk_bytes / 6; });
 }
 
 nvcompStatus_t nvcompBatchedSnappyCompressAsync(

@@ -1,7 +1,8 @@
 /*
  * api/zstd_api.hip -- C ABI of the batched Zstandard decoder (include/nvcomp/zstd.h) and the kernels it launches. Host
  * side does argument checks, one 4-byte memset of the ticket counter and one launch per *Async call on the caller's
- * stream; nothing here allocates or synchronises.
+ * stream; nothing here allocates or synchronises. The batch, the ticket and the argument checks are common/api_batch.hip.h;
+ * the kernels spell their frames out, because the compiler writes them differently otherwise (profiles/api_frame_shared.md).
  */
 #include <hip/hip_runtime.h>
 
@@ -9,27 +10,22 @@
 
 #include "nvcomp/zstd.h"
 
-#include "common/api_launch.h"
+#include "common/api_batch.hip.h"
 #include "common/log.h"
-#include "common/lz_launch.hip.h"
 
 #include "zstd/zstd_decode.hip.h"
 
 namespace {
 
 /* One wave per workgroup (chunks of a mixed batch take very different times: api/deflate_api.hip), persistent: a wave
- * that finishes a chunk draws the next one from the ticket counter (common/lz_launch.hip.h). zstd::kLdsPerWave =
+ * that finishes a chunk draws the next one from the ticket counter (common/api_batch.hip.h). zstd::kLdsPerWave =
  * 9.1 KiB would allow 17 waves per CU; the registers (130 VGPRs, no scratch) allow 3 per SIMD = 12 per CU. */
 constexpr unsigned kDecWavesPerSimd = 3;
-constexpr uint32_t kMaxOutCap = 1u << 26;
 constexpr size_t kMaxSlot = zstd::kBlockMax;
 
-struct ZstdLaunch
+struct ZstdLaunch : lzl::Tickets /* first_dynamic = waves of the launch */
 {
-  lzl::Batch b;
-  uint32_t* ticket;
-  size_t first_dynamic; /* = waves of the launch */
-  uint8_t* slots;       /* slot_bytes per wave of the launch */
+  uint8_t* slots; /* slot_bytes per wave of the launch */
   size_t slot_bytes;
 };
 
@@ -48,8 +44,8 @@ __global__ void __launch_bounds__(64, kDecWavesPerSimd) zstd_decompress_kernel(c
     uint8_t* out = wave::uniform_ptr((uint8_t*)a->b.out_ptrs[chunk]);
     const size_t in_len64 = wave::uniform64(a->b.comp_bytes[chunk]);
     size_t cap64 = wave::uniform64(a->b.out_caps[chunk]);
-    if (cap64 > kMaxOutCap) {
-      cap64 = kMaxOutCap;
+    if (cap64 > lzl::kMaxOutCap) {
+      cap64 = lzl::kMaxOutCap;
     }
     uint8_t* slot = wave::uniform_ptr(a->slots + wave_id * a->slot_bytes);
     const uint32_t slot_cap = (uint32_t)a->slot_bytes;
@@ -136,44 +132,40 @@ nvcompStatus_t nvcompBatchedZstdDecompressAsync(
   nvlog::call(3, "nvcompBatchedZstdDecompressAsync(batch_size=%zu, temp_bytes=%zu, statuses=%s, actual_sizes=%s, stream=%p)",
               batch_size, temp_bytes, device_statuses ? "yes" : "null", device_actual_uncompressed_bytes ? "yes" : "null",
               (void*)stream);
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_compressed_ptrs == nullptr || device_compressed_bytes == nullptr || device_uncompressed_bytes == nullptr
-      || device_uncompressed_ptrs == nullptr || device_temp_ptr == nullptr || ((uintptr_t)device_temp_ptr & 15u) != 0
-      || temp_bytes < zstd::kTempHeader + 16) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  /* as many waves as stay resident (at most kMaxWaves, at most one per chunk), each with its literal slot */
-  static lzl::ResidentCache resident; /* per device ordinal */
-  size_t waves = resident.get(zstd_decompress_kernel, 64, 0);
-  if (waves == 0 || waves > zstd::kMaxWaves) {
-    waves = zstd::kMaxWaves;
-  }
-  if (waves > batch_size) {
-    waves = batch_size;
-  }
-  size_t slot = ((temp_bytes - zstd::kTempHeader) / waves) & ~(size_t)15;
-  if (slot > kMaxSlot) {
-    slot = kMaxSlot;
-  }
-  if (slot < 16) { /* a buffer sized for fewer chunks than the launch has waves: fewer waves */
-    slot = 16;
-    waves = (temp_bytes - zstd::kTempHeader) / slot;
-  }
-  uint32_t* ticket = nullptr;
-  if (waves < batch_size) {
-    if (hipMemsetAsync(device_temp_ptr, 0, sizeof(uint32_t), stream) != hipSuccess) {
-      return nvcompErrorCudaError;
+  const bool arrays_ok = lzl::all_set(device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes, device_uncompressed_ptrs,
+                                      device_temp_ptr)
+                         && ((uintptr_t)device_temp_ptr & 15u) == 0 && temp_bytes >= zstd::kTempHeader + 16;
+  return lzl::checked_launch(batch_size, arrays_ok, [&]() -> nvcompStatus_t {
+    /* as many waves as stay resident (at most kMaxWaves, at most one per chunk), each with its literal slot */
+    static lzl::ResidentCache resident; /* per device ordinal */
+    size_t waves = resident.get(zstd_decompress_kernel, 64, 0);
+    if (waves == 0 || waves > zstd::kMaxWaves) {
+      waves = zstd::kMaxWaves;
     }
-    ticket = (uint32_t*)device_temp_ptr;
-  }
-  const lzl::Batch b = {device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
-                        device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, (int*)device_statuses};
-  const ZstdLaunch launch = {b, ticket, waves, (uint8_t*)device_temp_ptr + zstd::kTempHeader, slot};
-  hipLaunchKernelGGL(zstd_decompress_kernel, dim3((unsigned)waves), dim3(64), 0, stream, launch);
-  return launch_status();
+    if (waves > batch_size) {
+      waves = batch_size;
+    }
+    size_t slot = ((temp_bytes - zstd::kTempHeader) / waves) & ~(size_t)15;
+    if (slot > kMaxSlot) {
+      slot = kMaxSlot;
+    }
+    if (slot < 16) { /* a buffer sized for fewer chunks than the launch has waves: fewer waves */
+      slot = 16;
+      waves = (temp_bytes - zstd::kTempHeader) / slot;
+    }
+    uint32_t* ticket = nullptr;
+    if (waves < batch_size) {
+      if (hipMemsetAsync(device_temp_ptr, 0, sizeof(uint32_t), stream) != hipSuccess) {
+        return nvcompErrorCudaError;
+      }
+      ticket = (uint32_t*)device_temp_ptr;
+    }
+    const lzl::Batch b = {device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
+                          device_actual_uncompressed_bytes, batch_size, device_uncompressed_ptrs, (int*)device_statuses};
+    const ZstdLaunch launch = {{b, ticket, waves}, (uint8_t*)device_temp_ptr + zstd::kTempHeader, slot};
+    hipLaunchKernelGGL(zstd_decompress_kernel, dim3((unsigned)waves), dim3(64), 0, stream, launch);
+    return nvcompSuccess;
+  });
 }
 
 nvcompStatus_t nvcompBatchedZstdGetDecompressSizeAsync(
@@ -184,16 +176,8 @@ nvcompStatus_t nvcompBatchedZstdGetDecompressSizeAsync(
     hipStream_t stream)
 {
   nvlog::call(3, "nvcompBatchedZstdGetDecompressSizeAsync(batch_size=%zu, stream=%p)", batch_size, (void*)stream);
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (device_compressed_ptrs == nullptr || device_compressed_bytes == nullptr || device_uncompressed_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  hipLaunchKernelGGL(zstd_size_kernel, dim3((unsigned)((batch_size + 255) / 256)), dim3(256), 0, stream,
-                     device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes, batch_size);
-  return launch_status();
+  return lzl::size_by_lane_async<zstd_size_kernel>(device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
+                                                   batch_size, stream);
 }
 
 } // extern "C"

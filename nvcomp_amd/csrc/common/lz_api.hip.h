@@ -1,7 +1,7 @@
 /*
- * common/lz_api.hip.h -- what api/lz4_api.hip and api/snappy_api.hip have in common: the bodies of their kernels around
- * the format's decode / encode call, the persistent-or-static launch, the dispatch by batch size (common/lz_launch.hip.h)
- * and the argument checks of the entry points.
+ * common/lz_api.hip.h -- what api/lz4_api.hip and api/snappy_api.hip have in common beyond what every format has
+ * (common/api_batch.hip.h: the chunk frame, the persistent launch, the argument checks): the bodies of their window, pair,
+ * team and compress kernels around the format's decode / encode call, and the dispatch by batch size (common/lz_launch.hip.h).
  *
  * The __global__ functions stay in the two files, under their own names and with their __shared__ arrays; each declares
  * its LDS and calls a body here. A FORMAT is a struct of static functions (Lz4, Snappy in the two files):
@@ -16,7 +16,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "common/api_launch.h"
 #include "common/log.h"
 #include "common/lz_launch.hip.h"
 #include "common/lz_window.hip.h"
@@ -43,43 +42,6 @@ namespace lzl {
 constexpr unsigned kDecWaves = NVCOMP_LZ_DEC_WAVES_PER_BLOCK;
 constexpr unsigned kEncWaves = NVCOMP_LZM_WAVES_PER_BLOCK; /* the compressors' workgroup size */
 constexpr unsigned kWideWaves = NVCOMP_LZMW_WAVES_PER_BLOCK;
-
-/* One chunk of a decompress call as the wave (or workgroup) that decodes it reads it, wave-uniform. */
-struct Chunk
-{
-  const uint8_t* in;
-  uint8_t* out;
-  size_t in_len;
-  size_t cap; /* at most kMaxOutCap */
-  __device__ __forceinline__ bool too_long() const { return in_len > 0xffffffffull - 64; }
-};
-
-template <class BatchPtr>
-__device__ __forceinline__ Chunk fetch_chunk(BatchPtr b, size_t chunk)
-{
-  Chunk c;
-  c.in = wave::uniform_ptr((const uint8_t*)b->comp_ptrs[chunk]);
-  c.out = wave::uniform_ptr((uint8_t*)b->out_ptrs[chunk]);
-  c.in_len = wave::uniform64(b->comp_bytes[chunk]);
-  c.cap = wave::uniform64(b->out_caps[chunk]);
-  if (c.cap > kMaxOutCap) {
-    c.cap = kMaxOutCap;
-  }
-  return c;
-}
-
-/* The chunk's size and status, by one lane (the caller picks it). */
-template <bool CHECKED, class BatchPtr>
-__device__ __forceinline__ void report(BatchPtr b, size_t chunk, uint32_t produced, uint32_t err)
-{
-  size_t* actual_bytes = b->actual_bytes;
-  if (actual_bytes != nullptr) {
-    actual_bytes[chunk] = err ? 0 : produced;
-  }
-  if (CHECKED && b->statuses != nullptr) {
-    b->statuses[chunk] = err ? nvcompErrorCannotDecompress : nvcompSuccess;
-  }
-}
 
 /* One wave (`w` of its workgroup) per chunk at a time; with a ticket counter the waves are persistent (common/lz_launch.hip.h).
  * decode(chunk, launch arguments, err) -> bytes produced, for chunks that are not too long. */
@@ -218,27 +180,6 @@ __device__ __forceinline__ void decode_team_loop(const Launch& launch, uint8_t* 
 #endif
 }
 
-/* One wave per chunk: size_of(in, in_len) -> what the stream says it decodes to (0: malformed). */
-template <class SizeOf>
-__device__ __forceinline__ void decompress_size(
-    const void* const* __restrict__ comp_ptrs, const size_t* __restrict__ comp_bytes, size_t* uncompressed_bytes,
-    size_t batch_size, SizeOf size_of)
-{
-  const size_t chunk = (size_t)blockIdx.x * kWavesPerBlock + wave::uniform(threadIdx.x >> 6);
-  if (chunk >= batch_size) {
-    return;
-  }
-  const uint8_t* in = wave::uniform_ptr((const uint8_t*)comp_ptrs[chunk]);
-  const size_t in_len64 = wave::uniform64(comp_bytes[chunk]);
-  uint32_t produced = 0;
-  if (in_len64 <= 0xffffffffull - 8) {
-    produced = size_of(in, (uint32_t)in_len64);
-  }
-  if (wave::lane_id() == 0) {
-    uncompressed_bytes[chunk] = produced;
-  }
-}
-
 /* The compressors: wave `w` of workgroups of WAVES; persistent waves, as in the decoders (common/lz_launch.hip.h): chunks of
  * a batch compress at very different speeds. encode(src, n, dst) -> bytes written. */
 template <unsigned WAVES, class Encode>
@@ -270,37 +211,6 @@ __device__ __forceinline__ void compress_loop(const CompressLaunch& launch, uint
 
 /* ---- host side ---- */
 
-/* Launch Kernel over a batch, `places` chunks per workgroup at a time. Persistent when the caller's temp buffer
- * can hold the ticket counter: as many workgroups as stay resident (at most `max_per_cu` per CU; 0: no cap), the rest of
- * the batch by ticket. Otherwise one place per chunk, statically. make_args(ticket, first_dynamic) -> the kernel's parameter. */
-template <auto Kernel, class MakeArgs>
-static inline void launch_persistent(
-    hipStream_t stream, void* temp, size_t temp_bytes, size_t batch_size, unsigned places, unsigned block_threads,
-    int max_per_cu, MakeArgs make_args)
-{
-  unsigned groups = (unsigned)((batch_size + places - 1) / places);
-  uint32_t* ticket = nullptr;
-  if (temp != nullptr && temp_bytes >= sizeof(uint32_t) && ((uintptr_t)temp & 3u) == 0) {
-    static ResidentCache resident; /* per kernel; inside, per device ordinal */
-    const unsigned fit = resident.get(Kernel, block_threads, max_per_cu);
-    if (fit != 0 && fit < groups && hipMemsetAsync(temp, 0, sizeof(uint32_t), stream) == hipSuccess) {
-      ticket = (uint32_t*)temp;
-      groups = fit;
-    }
-  }
-  const auto args = make_args(ticket, (size_t)groups * places);
-  hipLaunchKernelGGL(Kernel, dim3(groups), dim3(block_threads), 0, stream, args);
-}
-
-static inline nvcompStatus_t temp_size(size_t num_chunks, size_t* temp_bytes, size_t bytes = kTicketBytes)
-{
-  if (temp_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  *temp_bytes = num_chunks == 0 ? 0 : bytes;
-  return nvcompSuccess;
-}
-
 /* nvcompBatched<format>DecompressAsync with the format's four kernels: which one runs is decided by the batch size alone.
  * with_index: the one-wave-per-chunk launch gets the token-index slices of the temp buffer when it has room for them. */
 template <auto Team16, auto Team8, auto Pair, auto Window>
@@ -311,62 +221,30 @@ static inline nvcompStatus_t decompress_async(
 {
   nvlog::call(3, "nvcompBatched%sDecompressAsync(batch_size=%zu, statuses=%s, actual_sizes=%s, temp_bytes=%zu, stream=%p)", format,
               batch_size, statuses ? "yes" : "null", actual_bytes ? "yes" : "null", temp_bytes, (void*)stream);
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (comp_ptrs == nullptr || comp_bytes == nullptr || out_caps == nullptr || out_ptrs == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
   /* Bounds are checked whether or not the caller asked for statuses (round 4): the kernels without the checks were no
    * faster (655-668 against 675 GB/s on the headline batch over three evidence runs: the checks are a handful of
    * wave-uniform tests per batch), and a corrupt stream decoded with statuses == NULL could write past its output slot.
    * A NULL status array only means that nobody is told: a failed chunk still reads 0 in actual_bytes. */
   const Batch b = {comp_ptrs, comp_bytes, out_caps, actual_bytes, batch_size, out_ptrs, (int*)statuses};
-  if (batch_size <= kTeam16MaxBatch) {
-    /* at most one chunk per CU: sixteen waves a chunk (one team holds a whole CU's LDS budget for two) */
-    const Launch one_each = {b, nullptr, batch_size, nullptr};
-    hipLaunchKernelGGL(Team16, dim3((unsigned)batch_size), dim3(1024), 0, stream, one_each);
-  } else if (batch_size <= kTeamMaxBatch) {
-    /* small batches cannot fill the card with one wave per chunk: a workgroup per chunk (common/lz_team.hip.h) */
-    launch_persistent<Team8>(stream, temp, temp_bytes, batch_size, 1, 512, 0,
-                             [&](uint32_t* ticket, size_t first_dynamic) { return Launch{b, ticket, first_dynamic, nullptr}; });
-  } else if (batch_size <= kPairMaxBatch) {
-    /* (round 2's path for small batches: two waves per chunk, producer / consumer) */
-    hipLaunchKernelGGL(Pair, dim3((unsigned)batch_size), dim3(128), 0, stream, b);
-  } else {
-    launch_persistent<Window>(stream, temp, temp_bytes, batch_size, kDecWaves, 64 * kDecWaves, NVCOMP_LZ_MAX_WG_PER_CU,
-                              [&](uint32_t* ticket, size_t waves) {
-                                return Launch{b, ticket, waves, with_index ? index_base(temp, temp_bytes, waves) : nullptr};
-                              });
-  }
-  return launch_status();
-}
-
-/* nvcompBatched<format>GetDecompressSizeAsync with the format's size kernel. */
-template <auto Kernel>
-static inline nvcompStatus_t decompress_size_async(
-    const void* const* comp_ptrs, const size_t* comp_bytes, size_t* uncompressed_bytes, size_t batch_size, hipStream_t stream)
-{
-  if (batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (comp_ptrs == nullptr || comp_bytes == nullptr || uncompressed_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  hipLaunchKernelGGL(Kernel, dim3(grid_for(batch_size)), dim3(64 * kWavesPerBlock), 0, stream, comp_ptrs, comp_bytes,
-                     uncompressed_bytes, batch_size);
-  return launch_status();
-}
-
-/* What the three compress entry points check first: `opts_ok` is the format's verdict on its options. */
-static inline nvcompStatus_t compress_opts_status(bool opts_ok, size_t max_chunk_bytes, size_t limit)
-{
-  if (!opts_ok) {
-    return nvcompErrorInvalidValue;
-  }
-  return max_chunk_bytes > limit ? nvcompErrorChunkSizeTooLarge : nvcompSuccess;
+  return checked_launch(batch_size, all_set(comp_ptrs, comp_bytes, out_caps, out_ptrs), [&] {
+    if (batch_size <= kTeam16MaxBatch) {
+      /* at most one chunk per CU: sixteen waves a chunk (one team holds a whole CU's LDS budget for two) */
+      const Launch one_each = {{b, nullptr, batch_size}, nullptr};
+      hipLaunchKernelGGL(Team16, dim3((unsigned)batch_size), dim3(1024), 0, stream, one_each);
+    } else if (batch_size <= kTeamMaxBatch) {
+      /* small batches cannot fill the card with one wave per chunk: a workgroup per chunk (common/lz_team.hip.h) */
+      launch_persistent<Team8>(stream, temp, temp_bytes, batch_size, 1, 512, 0,
+                               [&](uint32_t* ticket, size_t first_dynamic) { return Launch{{b, ticket, first_dynamic}, nullptr}; });
+    } else if (batch_size <= kPairMaxBatch) {
+      /* (round 2's path for small batches: two waves per chunk, producer / consumer) */
+      hipLaunchKernelGGL(Pair, dim3((unsigned)batch_size), dim3(128), 0, stream, b);
+    } else {
+      launch_persistent<Window>(stream, temp, temp_bytes, batch_size, kDecWaves, 64 * kDecWaves, NVCOMP_LZ_MAX_WG_PER_CU,
+                                [&](uint32_t* ticket, size_t waves) {
+                                  return Launch{{b, ticket, waves}, with_index ? index_base(temp, temp_bytes, waves) : nullptr};
+                                });
+    }
+  });
 }
 
 /* The arguments of nvcompBatched<format>CompressAsync, behind the format's name and compress_opts_status(). */
@@ -395,19 +273,13 @@ static inline nvcompStatus_t compress_async(const CompressCall& c)
   if (c.opts_status != nvcompSuccess) {
     return c.opts_status;
   }
-  if (c.batch_size == 0) {
-    return nvcompSuccess;
-  }
-  if (c.in_ptrs == nullptr || c.in_bytes == nullptr || c.out_ptrs == nullptr || c.out_bytes == nullptr) {
-    return nvcompErrorInvalidValue;
-  }
-  clear_stale_error();
-  launch_persistent<Kernel>(c.stream, c.temp, c.temp_bytes, c.batch_size, WAVES, 64 * WAVES, 0,
-                            [&](uint32_t* ticket, size_t first_dynamic) {
-                              return CompressLaunch{c.in_ptrs, c.in_bytes, c.max_chunk_bytes, c.batch_size,
-                                                    c.out_ptrs, c.out_bytes, ticket, first_dynamic};
-                            });
-  return launch_status();
+  return checked_launch(c.batch_size, all_set(c.in_ptrs, c.in_bytes, c.out_ptrs, c.out_bytes), [&] {
+    launch_persistent<Kernel>(c.stream, c.temp, c.temp_bytes, c.batch_size, WAVES, 64 * WAVES, 0,
+                              [&](uint32_t* ticket, size_t first_dynamic) {
+                                return CompressLaunch{c.in_ptrs, c.in_bytes, c.max_chunk_bytes, c.batch_size,
+                                                      c.out_ptrs, c.out_bytes, ticket, first_dynamic};
+                              });
+  });
 }
 
 } // namespace lzl

@@ -16,17 +16,16 @@
  * compile-time constants: the library has no run-time tuning state (tests force each path with an A/B build of this
  * file's macros).
  *
- * This file holds the thresholds, the kernels' parameter structs and the residency query. The launches themselves
- * (persistent or static, the dispatch by batch size) and the kernel bodies LZ4 and Snappy share are common/lz_api.hip.h.
+ * This file holds the thresholds, the token-index layout of the temp buffer and the kernels' parameter structs. What a
+ * launch needs whatever the format (the batch, the ticket, the residency query, the persistent launch itself) is
+ * common/api_batch.hip.h; the kernel bodies LZ4 and Snappy share and the dispatch by batch size are common/lz_api.hip.h.
  */
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
-
-#include "common/wave.h"
+#include "common/api_batch.hip.h"
 
 #ifndef NVCOMP_LZ_PAIR_MAX_BATCH
 #define NVCOMP_LZ_PAIR_MAX_BATCH 4096 /* two waves per chunk up to here: 319 against 310 GB/s at 4 096 chunks since the pair kernels lost their scratch
@@ -54,10 +53,8 @@ namespace lzl {
 constexpr size_t kPairMaxBatch = (size_t)(NVCOMP_LZ_PAIR_MAX_BATCH);
 constexpr size_t kTeamMaxBatch = (size_t)(NVCOMP_LZ_TEAM_MAX_BATCH);
 constexpr size_t kTeam16MaxBatch = (size_t)(NVCOMP_LZ_TEAM16_MAX_BATCH) < kTeamMaxBatch ? (size_t)(NVCOMP_LZ_TEAM16_MAX_BATCH) : kTeamMaxBatch;
-constexpr uint32_t kMaxOutCap = 1u << 26;
-constexpr size_t kTicketBytes = 16; /* what the temp-size queries ask for: one u32 counter, padded */
-/* ... and, for the persistent one-wave-per-chunk launches, room for every wave's token index (common/lz_index.hip.h:
- * 64 lists of 344 positions of 16 bits) behind it. The queries cannot ask the device how many waves stay resident: they assume at
+/* The temp buffer: the ticket counter (kTicketBytes) and, for the persistent one-wave-per-chunk launches, room for every
+ * wave's token index (common/lz_index.hip.h: 64 lists of 344 positions of 16 bits) behind it. The queries cannot ask the device how many waves stay resident: they assume at
  * most kIndexMaxWaves (MI355X: 256 CUs x 28 = 7 168); a launch with more waves, or a caller with a smaller buffer, decodes
  * without the index (same bytes, the round-5 speed). */
 constexpr size_t kIndexOffset = 64;
@@ -77,26 +74,10 @@ inline uint8_t* index_base(void* temp, size_t temp_bytes, size_t waves)
   return (uint8_t*)temp + kIndexOffset;
 }
 
-/* The caller's arrays of one nvcompBatched<Fmt>DecompressAsync call. */
-struct Batch
+/* The single parameter of the persistent decode kernels (Tickets: common/api_batch.hip.h). */
+struct Launch : Tickets
 {
-  const void* const* comp_ptrs;
-  const size_t* comp_bytes;
-  const size_t* out_caps;
-  size_t* actual_bytes;
-  size_t batch_size;
-  void* const* out_ptrs;
-  int* statuses; /* nvcompStatus_t* */
-};
-
-/* The single parameter of the persistent kernels: the batch, the ticket counter (NULL: one chunk per wave, statically) and
- * the first chunk index handed out by ticket (= waves of the launch). Read through wave::kernel_args where needed. */
-struct Launch
-{
-  Batch b;
-  uint32_t* ticket;
-  size_t first_dynamic;
-  uint8_t* index;        /* kIndexBytesPerWave bytes per wave of the launch for the token index (common/lz_index.hip.h); NULL: no index */
+  uint8_t* index; /* kIndexBytesPerWave bytes per wave of the launch for the token index (common/lz_index.hip.h); NULL: no index */
 };
 
 /* The same for the compressors: the caller's arrays of one nvcompBatched<Fmt>CompressAsync call. */
@@ -110,66 +91,6 @@ struct CompressLaunch
   size_t* out_bytes;
   uint32_t* ticket;
   size_t first_dynamic;
-};
-
-/* The wave's next chunk: `first_dynamic` + a ticket (lane 0 draws it, the wave shares it). */
-__device__ __forceinline__ size_t next_chunk(uint32_t* ticket, size_t first_dynamic)
-{
-  uint32_t t = 0;
-  if (wave::lane_id() == 0) {
-    t = atomicAdd(ticket, 1u);
-  }
-  return first_dynamic + wave::uniform(wave::read_lane(t, 0));
-}
-
-/* Workgroups of `kernel` (block threads, static LDS) the current device keeps resident at once; 0 when the runtime
- * cannot tell (the launch is then static). */
-template <class Kernel>
-inline unsigned resident_workgroups(Kernel kernel, unsigned block_threads, int max_per_cu = NVCOMP_LZ_MAX_WG_PER_CU, int* device = nullptr)
-{
-  int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess
-      || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess
-      || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, (int)block_threads, 0) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  if (device != nullptr) {
-    *device = dev;
-  }
-  if (max_per_cu > 0 && per_cu > max_per_cu) {
-    per_cu = max_per_cu;
-  }
-  return cus > 0 && per_cu > 0 ? (unsigned)cus * (unsigned)per_cu : 0u;
-}
-
-/* The same, remembered PER DEVICE ORDINAL (one instance per kernel, a function-local static of the caller): a process
- * that drives several cards from one thread (benchmarks/benchmark_allgather.cpp: hipSetDevice in a loop) gets each
- * card's own geometry, and the two runtime queries are made once per kernel and card. Lock-free; two threads racing on
- * the first call both ask and store the same answer. */
-struct ResidentCache
-{
-  static constexpr int kDevices = 64;
-  std::atomic<unsigned> known[kDevices] = {}; /* answer + 1; 0 = not asked yet */
-  template <class Kernel>
-  unsigned get(Kernel kernel, unsigned block_threads, int max_per_cu = NVCOMP_LZ_MAX_WG_PER_CU)
-  {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-      (void)hipGetLastError();
-      return 0;
-    }
-    if (dev < 0 || dev >= kDevices) {
-      return resident_workgroups(kernel, block_threads, max_per_cu);
-    }
-    const unsigned seen = known[dev].load(std::memory_order_relaxed);
-    if (seen != 0) {
-      return seen - 1;
-    }
-    const unsigned fit = resident_workgroups(kernel, block_threads, max_per_cu);
-    known[dev].store(fit + 1, std::memory_order_relaxed);
-    return fit;
-  }
 };
 
 } // namespace lzl

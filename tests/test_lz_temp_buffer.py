@@ -1,4 +1,4 @@
-"""The LZ4 / Snappy launches with every kind of temp buffer. One helper (common/lz_api.hip.h: launch_persistent) decides
+"""The LZ4 / Snappy launches with every kind of temp buffer. One helper (common/api_batch.hip.h: launch_persistent) decides
 between persistent waves drawing tickets from the caller's temp buffer and one place per chunk, statically: a buffer that
 is NULL, misaligned or too small for the counter must give the same bytes as the one the size query asks for."""
 import numpy as np

@@ -32,22 +32,6 @@ nvcompStatus_t nvcompAmdBatchedPackAsync(
     size_t* device_offsets,
     hipStream_t stream);
 
-/* The token index that nvcompBatched{LZ4,Snappy}DecompressAsync builds per chunk when a batch runs on its persistent
- * one-wave-per-chunk kernels and the temp buffer has the size nvcompBatched<Fmt>DecompressGetTempSize reports
- * (csrc/common/lz_index.hip.h): the stream offsets of a PREFIX of the chunk's sequences, found by 64 joined serial walks,
- * and the offset where the decoder's classic token chase takes over. Exposed for inspection and tests: after the call (on
- * `stream`) chunk i has device_info[2 i] positions in device_lists[22016 i ...] (16 bits each, increasing; 22 016 =
- * 64 x 344 entries of room per chunk) and
- * device_info[2 i + 1] = the offset of the first sequence that is not in the list (0 entries, offset 0: a stream the
- * index is not made for -- shorter than 2 KiB, longer than 65 535 bytes). */
-nvcompStatus_t nvcompAmdBatchedLZ4TokenIndexAsync(
-    const void* const* device_compressed_ptrs,
-    const size_t* device_compressed_bytes,
-    size_t batch_size,
-    unsigned short* device_lists,
-    unsigned* device_info,
-    hipStream_t stream);
-
 #ifdef __cplusplus
 }
 #endif

@@ -156,9 +156,6 @@ def declare(lib: C.CDLL, formats=FORMATS) -> C.CDLL:
         lib.bitcompMaxBuflen.argtypes, lib.bitcompMaxBuflen.restype = [sz], sz
     if hasattr(lib, "nvcompAmdBatchedPackAsync"):  # include/nvcomp/amd_ext.h
         lib.nvcompAmdBatchedPackAsync.argtypes = [vp, vp, sz, vp, sz, vp, vp]
-    if hasattr(lib, "nvcompAmdBatchedLZ4TokenIndexAsync"):  # LZ4 only: Snappy has no token index
-        lib.nvcompAmdBatchedLZ4TokenIndexAsync.argtypes = [vp, vp, sz, vp, vp, vp]
-        lib.nvcompAmdBatchedLZ4TokenIndexAsync.restype = C.c_int
     return lib
 
 

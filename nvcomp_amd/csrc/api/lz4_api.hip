@@ -10,8 +10,6 @@
 
 #include "nvcomp/lz4.h"
 
-#include "nvcomp/amd_ext.h"
-
 #include "common/lz_api.hip.h"
 #include "lz4/lz4_decode_window.hip.h"
 #include "lz4/lz4_encode.hip.h"
@@ -27,19 +25,6 @@ using lzl::kWideWaves;
 #define NVCOMP_LZ4_RUNS_RATIO 8
 #endif
 constexpr size_t kRunsRatio = NVCOMP_LZ4_RUNS_RATIO;
-#ifndef NVCOMP_LZ_INDEX
-#define NVCOMP_LZ_INDEX 0 /* 1: the persistent one-wave-per-chunk kernel finds its sequences with the token index
-                           * (common/lz_index.hip.h). Built, parity-green and measured in round 6 (profiles/r06_token_index.json,
-                           * gpurun r6e ... r6k): 26 % fewer vector instructions per launch, and SLOWER -- 494 against 643 GB/s on the
-                           * headline batch: the index costs what the chase it replaces cost (built and thrown away: 500 GB/s), its
-                           * 310 wave-steps of ~55 instructions a chunk run with half the lanes idle. Off.
-                           * The macro selects the INSTANTIATION of lz4w::decode_chunk (its INDEXED parameter, kIndexed below):
-                           * with 0 the window kernel holds no index code or state at all and the launch reserves no temp bytes
-                           * for one; with 1 (the A/B build lib/alt/libnvcomp_index.so, the emulator's "index" variant, the
-                           * tests) the kernel decodes through the index whenever the launch's temp buffer has room for it. */
-#endif
-constexpr bool kIndexed = NVCOMP_LZ_INDEX != 0;
-static_assert(lzl::kIndexBytesPerWave >= lzx::kScratchPerWave, "a wave's slice of the temp buffer holds its token list");
 
 /* LZ4 as common/lz_api.hip.h sees it. */
 struct Lz4
@@ -53,28 +38,20 @@ struct Lz4
   template <bool CHECKED>
   static __device__ __forceinline__ uint32_t alone(const uint8_t* in, uint32_t n, uint8_t* out, uint32_t cap, uint8_t* lds, uint32_t& err)
   {
-    return lz4w::decode_chunk<CHECKED, true>(in, n, out, cap, lds, err, nullptr);
+    return lz4w::decode_chunk<CHECKED, true>(in, n, out, cap, lds, err);
   }
 };
 
 template <bool CHECKED>
-__global__ void __launch_bounds__(64 * kDecWaves, NVCOMP_LZW_WAVES_PER_SIMD) lz4_decompress_window_kernel(const lzl::Launch launch)
+__global__ void __launch_bounds__(64 * kDecWaves, NVCOMP_LZW_WAVES_PER_SIMD) lz4_decompress_window_kernel(const lzl::Tickets launch)
 {
   __shared__ __attribute__((aligned(16))) uint8_t lds[kDecWaves][lzw::kLdsPerWave];
   const uint32_t w = wave::uniform(threadIdx.x >> 6);
-  lzl::decode_window_loop<CHECKED>(launch, w, [&](const lzl::Chunk& c, const auto* a, uint32_t& err) -> uint32_t {
-    /* the wave's slice of the temp buffer for the token index (the same for every chunk it decodes) */
-    uint8_t* index = nullptr;
-    if constexpr (kIndexed) {
-      index = a->index;
-      if (index != nullptr) {
-        index += ((size_t)blockIdx.x * kDecWaves + w) * lzl::kIndexBytesPerWave;
-      }
-    }
+  lzl::decode_window_loop<CHECKED>(launch, w, [&](const lzl::Chunk& c, uint32_t& err) -> uint32_t {
     if (Lz4::runs(c.in_len, c.cap)) {
-      return lz4w::decode_chunk<CHECKED, true, kIndexed>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err, index);
+      return lz4w::decode_chunk<CHECKED, true>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err);
     }
-    return lz4w::decode_chunk<CHECKED, false, kIndexed>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err, index);
+    return lz4w::decode_chunk<CHECKED, false>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err);
   });
 }
 
@@ -86,47 +63,10 @@ __global__ void __launch_bounds__(128, 7) lz4_decompress_pair_kernel(const lzl::
 }
 
 template <bool CHECKED, uint32_t WAVES>
-__global__ void __launch_bounds__(64 * WAVES, 4) lz4_decompress_team_kernel(const lzl::Launch launch)
+__global__ void __launch_bounds__(64 * WAVES, 4) lz4_decompress_team_kernel(const lzl::Tickets launch)
 {
   __shared__ __attribute__((aligned(16))) uint8_t lds[lzt::Geo<WAVES>::kLds];
   lzl::decode_team_loop<CHECKED, WAVES, Lz4>(launch, lds);
-}
-
-
-/* Inspection (include/nvcomp/amd_ext.h): the token index of every chunk, one wave each. */
-__global__ void __launch_bounds__(64) lz4_token_index_kernel(
-    const void* const* __restrict__ comp_ptrs, const size_t* __restrict__ comp_bytes, size_t batch_size, uint16_t* lists,
-    uint32_t* info)
-{
-  __shared__ __attribute__((aligned(16))) uint8_t lds[lzx::kLdsBytes];
-  const size_t chunk = blockIdx.x;
-  if (chunk >= batch_size) {
-    return;
-  }
-  const uint8_t* in = wave::uniform_ptr((const uint8_t*)comp_ptrs[chunk]);
-  const size_t in_len64 = wave::uniform64(comp_bytes[chunk]);
-  /* the lists are built in the caller's buffer (64 x kLaneCap entries per chunk) and compacted in place: list k moves
-   * down behind list k - 1 (its destination never lies behind its source) */
-  uint16_t* mine = lists + chunk * (64 * (size_t)lzx::kLaneCap);
-  lzx::Index ix = lzx::build<lz4w::IndexFormat>(in, in_len64 <= lzx::kMaxStream ? (uint32_t)in_len64 : 0u, lds, (uint8_t*)mine);
-  uint32_t total = 0;
-  for (uint32_t k = 0; k < ix.lanes; ++k) {
-    const uint32_t nk = wave::read_lane(ix.n, k);
-    for (uint32_t base = 0; base < nk; base += 64) {
-      const uint32_t i = base + (uint32_t)wave::lane_id();
-      const uint32_t v = i < nk ? mine[k * lzx::kLaneCap + i] : 0u;
-      wave::sync();
-      if (i < nk) {
-        mine[total + i] = (uint16_t)v;
-      }
-      wave::sync();
-    }
-    total += nk;
-  }
-  if (wave::lane_id() == 0) {
-    info[2 * chunk] = total;
-    info[2 * chunk + 1] = ix.resume;
-  }
 }
 
 __global__ void __launch_bounds__(64 * kWavesPerBlock) lz4_decompress_size_kernel(
@@ -188,8 +128,7 @@ nvcompStatus_t nvcompBatchedLZ4DecompressGetTempSize(
     size_t num_chunks, size_t /*max_uncompressed_chunk_bytes*/, size_t* temp_bytes)
 {
   /* the ticket counter of the persistent waves / workgroups (common/lz_launch.hip.h) */
-  return lzl::temp_size(num_chunks, temp_bytes,
-                        num_chunks > lzl::kPairMaxBatch && NVCOMP_LZ_INDEX ? lzl::index_temp_bytes(num_chunks) : lzl::kTicketBytes);
+  return lzl::temp_size(num_chunks, temp_bytes, lzl::kTicketBytes);
 }
 
 NVCOMP_API_DECOMPRESS_TEMP_SIZE_EX(LZ4)
@@ -208,22 +147,8 @@ nvcompStatus_t nvcompBatchedLZ4DecompressAsync(
 {
   return lzl::decompress_async<lz4_decompress_team_kernel<true, 16>, lz4_decompress_team_kernel<true, 8>,
                                lz4_decompress_pair_kernel<true>, lz4_decompress_window_kernel<true>>(
-      "LZ4", NVCOMP_LZ_INDEX != 0, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
+      "LZ4", device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
       device_actual_uncompressed_bytes, batch_size, device_temp_ptr, temp_bytes, device_uncompressed_ptrs, device_statuses, stream);
-}
-
-nvcompStatus_t nvcompAmdBatchedLZ4TokenIndexAsync(
-    const void* const* device_compressed_ptrs,
-    const size_t* device_compressed_bytes,
-    size_t batch_size,
-    unsigned short* device_lists,
-    unsigned* device_info,
-    hipStream_t stream)
-{
-  return lzl::checked_launch(batch_size, lzl::all_set(device_compressed_ptrs, device_compressed_bytes, device_lists, device_info), [&] {
-    hipLaunchKernelGGL(lz4_token_index_kernel, dim3((unsigned)batch_size), dim3(64), 0, stream, device_compressed_ptrs,
-                       device_compressed_bytes, batch_size, (uint16_t*)device_lists, (uint32_t*)device_info);
-  });
 }
 
 nvcompStatus_t nvcompBatchedLZ4GetDecompressSizeAsync(

@@ -47,11 +47,11 @@ struct Snappy
 };
 
 template <bool CHECKED>
-__global__ void __launch_bounds__(64 * kDecWaves, NVCOMP_LZW_WAVES_PER_SIMD) snappy_decompress_window_kernel(const lzl::Launch launch)
+__global__ void __launch_bounds__(64 * kDecWaves, NVCOMP_LZW_WAVES_PER_SIMD) snappy_decompress_window_kernel(const lzl::Tickets launch)
 {
   __shared__ __attribute__((aligned(16))) uint8_t lds[kDecWaves][lzw::kLdsPerWave];
   const uint32_t w = wave::uniform(threadIdx.x >> 6);
-  lzl::decode_window_loop<CHECKED>(launch, w, [&](const lzl::Chunk& c, const auto*, uint32_t& err) -> uint32_t {
+  lzl::decode_window_loop<CHECKED>(launch, w, [&](const lzl::Chunk& c, uint32_t& err) -> uint32_t {
     if (Snappy::runs(c.in_len, c.cap)) {
       return snappyw::decode_chunk<CHECKED, true>(c.in, (uint32_t)c.in_len, c.out, (uint32_t)c.cap, lds[w], err);
     }
@@ -60,7 +60,7 @@ __global__ void __launch_bounds__(64 * kDecWaves, NVCOMP_LZW_WAVES_PER_SIMD) sna
 }
 
 template <bool CHECKED, uint32_t WAVES>
-__global__ void __launch_bounds__(64 * WAVES, 4) snappy_decompress_team_kernel(const lzl::Launch launch)
+__global__ void __launch_bounds__(64 * WAVES, 4) snappy_decompress_team_kernel(const lzl::Tickets launch)
 {
   __shared__ __attribute__((aligned(16))) uint8_t lds[lzt::Geo<WAVES>::kLds];
   lzl::decode_team_loop<CHECKED, WAVES, Snappy>(launch, lds);
@@ -143,7 +143,7 @@ nvcompStatus_t nvcompBatchedSnappyDecompressAsync(
 {
   return lzl::decompress_async<snappy_decompress_team_kernel<true, 16>, snappy_decompress_team_kernel<true, 8>,
                                snappy_decompress_pair_kernel<true>, snappy_decompress_window_kernel<true>>(
-      "Snappy", false, device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
+      "Snappy", device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
       device_actual_uncompressed_bytes, batch_size, device_temp_ptr, temp_bytes, device_uncompressed_ptrs, device_statuses, stream);
 }
 

@@ -44,9 +44,9 @@ constexpr unsigned kEncWaves = NVCOMP_LZM_WAVES_PER_BLOCK; /* the compressors' w
 constexpr unsigned kWideWaves = NVCOMP_LZMW_WAVES_PER_BLOCK;
 
 /* One wave (`w` of its workgroup) per chunk at a time; with a ticket counter the waves are persistent (common/lz_launch.hip.h).
- * decode(chunk, launch arguments, err) -> bytes produced, for chunks that are not too long. */
+ * decode(chunk, err) -> bytes produced, for chunks that are not too long. */
 template <bool CHECKED, class Decode>
-__device__ __forceinline__ void decode_window_loop(const Launch& launch, uint32_t w, Decode decode)
+__device__ __forceinline__ void decode_window_loop(const Tickets& launch, uint32_t w, Decode decode)
 {
   size_t place = (size_t)blockIdx.x * kDecWaves + w; /* the wave's place in the launch = its first chunk */
 #ifdef NVCOMP_LZW_PROF
@@ -65,7 +65,7 @@ __device__ __forceinline__ void decode_window_loop(const Launch& launch, uint32_
     if (c.too_long()) {
       err = lz::kErrInput;
     } else {
-      produced = decode(c, a, err);
+      produced = decode(c, err);
     }
     if (wave::lane_id() == 0) {
       report<CHECKED>(&a->b, chunk, produced, err);
@@ -124,7 +124,7 @@ __device__ __forceinline__ void decode_pair(const Batch& b, uint8_t* lds)
  * workgroups when the caller's temp buffer holds a ticket counter, one workgroup per chunk otherwise. `lds`: the
  * workgroup's lzt::Geo<WAVES>::kLds bytes. */
 template <bool CHECKED, uint32_t WAVES, class Format>
-__device__ __forceinline__ void decode_team_loop(const Launch& launch, uint8_t* lds)
+__device__ __forceinline__ void decode_team_loop(const Tickets& launch, uint8_t* lds)
 {
   size_t chunk = blockIdx.x;
 #ifdef NVCOMP_LZW_PROF
@@ -211,11 +211,10 @@ __device__ __forceinline__ void compress_loop(const CompressLaunch& launch, uint
 
 /* ---- host side ---- */
 
-/* nvcompBatched<format>DecompressAsync with the format's four kernels: which one runs is decided by the batch size alone.
- * with_index: the one-wave-per-chunk launch gets the token-index slices of the temp buffer when it has room for them. */
+/* nvcompBatched<format>DecompressAsync with the format's four kernels: which one runs is decided by the batch size alone. */
 template <auto Team16, auto Team8, auto Pair, auto Window>
 static inline nvcompStatus_t decompress_async(
-    const char* format, bool with_index, const void* const* comp_ptrs, const size_t* comp_bytes, const size_t* out_caps,
+    const char* format, const void* const* comp_ptrs, const size_t* comp_bytes, const size_t* out_caps,
     size_t* actual_bytes, size_t batch_size, void* temp, size_t temp_bytes, void* const* out_ptrs, nvcompStatus_t* statuses,
     hipStream_t stream)
 {
@@ -229,20 +228,18 @@ static inline nvcompStatus_t decompress_async(
   return checked_launch(batch_size, all_set(comp_ptrs, comp_bytes, out_caps, out_ptrs), [&] {
     if (batch_size <= kTeam16MaxBatch) {
       /* at most one chunk per CU: sixteen waves a chunk (one team holds a whole CU's LDS budget for two) */
-      const Launch one_each = {{b, nullptr, batch_size}, nullptr};
+      const Tickets one_each = {b, nullptr, batch_size};
       hipLaunchKernelGGL(Team16, dim3((unsigned)batch_size), dim3(1024), 0, stream, one_each);
     } else if (batch_size <= kTeamMaxBatch) {
       /* small batches cannot fill the card with one wave per chunk: a workgroup per chunk (common/lz_team.hip.h) */
       launch_persistent<Team8>(stream, temp, temp_bytes, batch_size, 1, 512, 0,
-                               [&](uint32_t* ticket, size_t first_dynamic) { return Launch{{b, ticket, first_dynamic}, nullptr}; });
+                               [&](uint32_t* ticket, size_t first_dynamic) { return Tickets{b, ticket, first_dynamic}; });
     } else if (batch_size <= kPairMaxBatch) {
       /* (round 2's path for small batches: two waves per chunk, producer / consumer) */
       hipLaunchKernelGGL(Pair, dim3((unsigned)batch_size), dim3(128), 0, stream, b);
     } else {
       launch_persistent<Window>(stream, temp, temp_bytes, batch_size, kDecWaves, 64 * kDecWaves, NVCOMP_LZ_MAX_WG_PER_CU,
-                                [&](uint32_t* ticket, size_t waves) {
-                                  return Launch{{b, ticket, waves}, with_index ? index_base(temp, temp_bytes, waves) : nullptr};
-                                });
+                                [&](uint32_t* ticket, size_t waves) { return Tickets{b, ticket, waves}; });
     }
   });
 }

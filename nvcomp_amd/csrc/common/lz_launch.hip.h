@@ -16,7 +16,7 @@
  * compile-time constants: the library has no run-time tuning state (tests force each path with an A/B build of this
  * file's macros).
  *
- * This file holds the thresholds, the token-index layout of the temp buffer and the kernels' parameter structs. What a
+ * This file holds the thresholds and the compressors' parameter struct (the decoders' is lzl::Tickets). What a
  * launch needs whatever the format (the batch, the ticket, the residency query, the persistent launch itself) is
  * common/api_batch.hip.h; the kernel bodies LZ4 and Snappy share and the dispatch by batch size are common/lz_api.hip.h.
  */
@@ -53,34 +53,7 @@ namespace lzl {
 constexpr size_t kPairMaxBatch = (size_t)(NVCOMP_LZ_PAIR_MAX_BATCH);
 constexpr size_t kTeamMaxBatch = (size_t)(NVCOMP_LZ_TEAM_MAX_BATCH);
 constexpr size_t kTeam16MaxBatch = (size_t)(NVCOMP_LZ_TEAM16_MAX_BATCH) < kTeamMaxBatch ? (size_t)(NVCOMP_LZ_TEAM16_MAX_BATCH) : kTeamMaxBatch;
-/* The temp buffer: the ticket counter (kTicketBytes) and, for the persistent one-wave-per-chunk launches, room for every
- * wave's token index (common/lz_index.hip.h: 64 lists of 344 positions of 16 bits) behind it. The queries cannot ask the device how many waves stay resident: they assume at
- * most kIndexMaxWaves (MI355X: 256 CUs x 28 = 7 168); a launch with more waves, or a caller with a smaller buffer, decodes
- * without the index (same bytes, the round-5 speed). */
-constexpr size_t kIndexOffset = 64;
-constexpr size_t kIndexBytesPerWave = 45056;
-constexpr size_t kIndexMaxWaves = 8192;
-inline size_t index_temp_bytes(size_t num_chunks)
-{
-  const size_t waves = (num_chunks + 3) & ~(size_t)3;
-  return kIndexOffset + (waves < kIndexMaxWaves ? waves : kIndexMaxWaves) * kIndexBytesPerWave;
-}
-/* the index slices of a launch of `waves` waves inside the caller's temp buffer, or NULL when it has no room for them */
-inline uint8_t* index_base(void* temp, size_t temp_bytes, size_t waves)
-{
-  if (temp == nullptr || ((uintptr_t)temp & 7u) != 0 || temp_bytes < kIndexOffset + waves * kIndexBytesPerWave) {
-    return nullptr;
-  }
-  return (uint8_t*)temp + kIndexOffset;
-}
-
-/* The single parameter of the persistent decode kernels (Tickets: common/api_batch.hip.h). */
-struct Launch : Tickets
-{
-  uint8_t* index; /* kIndexBytesPerWave bytes per wave of the launch for the token index (common/lz_index.hip.h); NULL: no index */
-};
-
-/* The same for the compressors: the caller's arrays of one nvcompBatched<Fmt>CompressAsync call. */
+/* The compressors' single parameter: the caller's arrays of one nvcompBatched<Fmt>CompressAsync call. */
 struct CompressLaunch
 {
   const void* const* in_ptrs;

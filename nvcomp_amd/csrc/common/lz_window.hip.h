@@ -62,23 +62,16 @@ __device__ __forceinline__ void drop_front(lz::Seq& s, uint32_t take, uint32_t c
  * compare ((x - lo) <= hi - lo), conditions that grow with the lane are tested once for the wave, and nothing is
  * masked that the callers' invariant already zeroes.
  */
-struct NoHook
-{
-  __device__ __forceinline__ void operator()() const {}
-};
 
 #ifndef NVCOMP_LZW_FAR_L4_FROM_F0
 #define NVCOMP_LZW_FAR_L4_FROM_F0 0 /* A/B: the last dword of a far match of up to 16 bytes out of its first load */
 #endif
-/* `after_far`: called once per batch behind the point where the far matches' loads have been waited for (the decoders
- * with a token index settle their prefetched positions there: common/lz_index.hip.h). */
 /* A batch's whole blocks are written to HBM at its end. (Round 6 tried writing them only when the window has to slide --
  * every third or fourth batch of text, 2 KiB at a time; nothing needs them earlier: LZ4 mix 683 -> 686 GB/s, Snappy mix
  * 501 -> 484, float32 column 412 -> 400. DESIGN.md, "retired switches".) */
-template <bool CHECKED, bool RING_LITERALS = false, class AfterFar = NoHook>
+template <bool CHECKED, bool RING_LITERALS = false>
 __device__ __forceinline__ uint32_t execute_window_batch(
-    InRing& ir, OutWindow& ow, uint32_t out_cap, uint32_t& op, uint32_t n, const lz::Seq& s, uint32_t& err, bool& big,
-    AfterFar after_far = AfterFar())
+    InRing& ir, OutWindow& ow, uint32_t out_cap, uint32_t& op, uint32_t n, const lz::Seq& s, uint32_t& err, bool& big)
 {
   const uint32_t lane = (uint32_t)wave::lane_id();
   const uint32_t len = s.lit_len + s.match_len;
@@ -260,7 +253,6 @@ __device__ __forceinline__ uint32_t execute_window_batch(
     }
   }
   wave::sync();
-  after_far();
   LZW_T(7);
 
   /* ---- remaining matches, oldest first: multi-round resolution in LDS ---- */

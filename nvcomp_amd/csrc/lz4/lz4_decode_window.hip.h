@@ -17,9 +17,6 @@
 #include "common/lz_window.hip.h"
 #include "common/lz_chase.hip.h"
 #include "common/lz_run_batch.hip.h"
-#include "common/lz_index.hip.h"
-
-#include <type_traits>
 
 namespace lz4w {
 
@@ -315,33 +312,6 @@ __device__ __forceinline__ void parse_batch(const R& r, uint32_t p, uint32_t fro
   }
 }
 
-/* What the token index (common/lz_index.hip.h) needs to know of the format: the size of ONE sequence in the stream, from
- * the 64 bytes a lane holds in its LDS block. Straight-line like DeltaFn::fast: one extension byte of the literal length,
- * up to two of the match length (matches to 528 bytes); anything longer is "cannot tell" -- the index ends there and the
- * chase above takes over. The bytes behind the literals are read whatever the token says (a read behind the block lands in
- * the wave's own LDS and is not used). */
-struct IndexFormat
-{
-  static __device__ __forceinline__ uint32_t first_token(const uint8_t*, uint32_t) { return 0; }
-  /* the token at block offset o (o + 1 < kBlock): true = its successor starts at next_o (which may lie behind the block:
-   * the walk refills there); false = the block does not hold what it takes (ok: a refill at the token will; !ok: never) */
-  static __device__ __forceinline__ bool step(const uint8_t* blk, uint32_t o, uint32_t& next_o, bool& ok)
-  {
-    const uint32_t t = blk[o], e1 = blk[o + 1];
-    const uint32_t code = t >> 4;
-    const bool c15 = code == 15;
-    const uint32_t d0 = 3 + code + (c15 ? e1 + 1u : 0u); /* to the byte a match-length extension would use */
-    const uint32_t o2 = o + d0;
-    const uint32_t e2 = blk[o2], e3 = blk[o2 + 1];
-    const bool m15 = (t & 15u) == 15u;
-    const bool fits = !m15 | (o2 + 1 < lzx::kBlock); /* only a long match looks at the bytes behind the offset */
-    const bool m2 = m15 & fits & (e2 == 255);
-    next_o = o2 + (m15 ? (m2 ? 2u : 1u) : 0u);
-    ok = !((c15 & (e1 == 255)) | (m2 & (e3 == 255)));
-    return ok & fits;
-  }
-};
-
 /* What the workgroup-per-chunk decoder (common/lz_team.hip.h) and the two-wave decoder (common/lz_pair.hip.h) need to know
  * of the format. */
 struct FrontEnd
@@ -384,48 +354,27 @@ struct FrontEnd
   static __device__ __forceinline__ uint32_t streamed_take(const lz::Seq&, uint32_t) { return 1; }
 };
 
-struct NoIndex
-{
-};
-
 /* Decode one chunk with the calling wave; `lds` is this wave's kLdsPerWave bytes. */
 /* RUNS: the loop tries lzw::execute_run_batch (sorted keys, typed columns). Its mere presence in the loop costs every
  * other kind of data 1.5-2 % (block placement and register allocation of the batch executor around it: gpurun r6u, r6v --
  * the same with the attempts gated off at run time), so the kernels instantiate the loop twice and pick per chunk by what
  * the stream shrank to (decode_one: runs only pay from 8 x on). */
-/* INDEXED: the sequences' positions come from the token index (common/lz_index.hip.h) as far as it reaches. A property of
- * the instantiation, not of the call: with `index_scratch` tested at run time the loop of every build kept the index's
- * reader, its branches and the three registers settle() holds across the far-match wait (928 of 5 591 vector instructions
- * of the kernel, 12 of 18 SGPR spills). false: no Index object exists and index_scratch is not looked at. */
-template <bool CHECKED, bool RUNS = false, bool INDEXED = false>
+template <bool CHECKED, bool RUNS = false>
 __device__ __forceinline__ uint32_t decode_chunk(
-    const uint8_t* __restrict__ in, uint32_t in_len, uint8_t* out, uint32_t out_cap, uint8_t* lds, uint32_t& err,
-    uint8_t* index_scratch = nullptr)
+    const uint8_t* __restrict__ in, uint32_t in_len, uint8_t* out, uint32_t out_cap, uint8_t* lds, uint32_t& err)
 {
   const uint32_t lane = (uint32_t)wave::lane_id();
   err = lz::kErrNone;
   if (in_len == 0) {
     return 0;
   }
-  /* where the sequences start: the token index (common/lz_index.hip.h) when the caller's temp buffer has room for it --
-   * a prefix of the chunk's tokens; the chase below takes over where it ends (at once without an index). The index is
-   * built in the LDS that the ring, the window and the jump tables use afterwards. */
-  static_assert(lzx::kLdsBytes <= lzw::kLdsPerWave, "the index is built in the wave's own LDS");
   LZW_T(9);
-  /* (an empty object when !INDEXED: nothing of it is read below) */
-  std::conditional_t<INDEXED, lzx::Index, NoIndex> ix;
-  uint32_t resume = 0;
-  if constexpr (INDEXED) {
-    ix = lzx::build<IndexFormat>(in, in_len, lds, index_scratch);
-    LZW_T(15); /* the token index */
-    resume = ix.resume;
-  }
   lzw::InRing ir;
   lzw::OutWindow ow;
   lzw::in_init(ir, in, in_len, lds + lzw::kOutLds);
   lzw::out_init(ow, out, lds);
   lzw::Chase c;
-  lzw::chase_init(c, ir.vbeg + resume, lds + lzw::kOutLds + lzw::kInLds);
+  lzw::chase_init(c, ir.vbeg, lds + lzw::kOutLds + lzw::kInLds);
   uint32_t op = 0;
   uint32_t seqpos = 0;
   uint32_t count = 0; /* sequences recorded in seqpos lanes [0, count) and not yet executed */
@@ -444,28 +393,16 @@ __device__ __forceinline__ uint32_t decode_chunk(
   s.match_off = 0;
   s.match_len = 0;
   for (;;) {
-    bool indexed = false;
-    if constexpr (INDEXED) {
-      indexed = lzx::more(ix);
-    }
-    if (count == 0 && !indexed && c.q >= ir.vend) {
+    const bool more = c.q < ir.vend; /* the chase has stream left */
+    if (count == 0 && !more) {
       break;
     }
     const uint32_t before = count; /* lanes [before, count) are parsed this round */
-    const bool refill = count < kRefillBelow && (indexed || c.q < ir.vend);
-    if (refill && indexed) {
-      if constexpr (INDEXED) {
-        /* the next token positions out of the index */
-        LZW_T(10);
-        count = lzx::read(ix, seqpos, count, ir.vbeg);
-        if (count == 0) {
-          continue; /* (the lists that were left held nothing: the chase takes over) */
-        }
-        const uint32_t oldest = wave::read_lane(seqpos, 0);
-        lzw::in_ensure(ir, oldest, (oldest & ~(lzw::kInBlock - 1)) + 3 * lzw::kInBlock);
-        LZW_T(0);
-      }
-    } else if (refill) {
+    const bool refill = count < kRefillBelow && more;
+    /* (`more` computed once, and chase and parse under a test of `refill` each, on purpose: with c.q compared where it is
+     * used the compiler rotates the loop, with one block it lays the kernels out anew, and both were measured --
+     * two waves per chunk lose 2-3 % at 4 096 chunks: profiles/lz_token_index_retired.md) */
+    if (refill) {
       /* keep the stream resident from the oldest unexecuted token to well past the chase */
       const uint32_t oldest = count ? wave::read_lane(seqpos, 0) : c.q;
       LZW_T(10);
@@ -496,12 +433,7 @@ __device__ __forceinline__ uint32_t decode_chunk(
       gate = wave::uniform(lzw::run_gate_tried(gate, take, misfit));
     }
     if (take == 0) {
-      auto settle = [&]() {
-        if constexpr (INDEXED) {
-          lzx::settle(ix);
-        }
-      };
-      take = lzw::execute_window_batch<CHECKED, false, decltype(settle)>(ir, ow, out_cap, op, count, s, err, big, settle);
+      take = lzw::execute_window_batch<CHECKED, false>(ir, ow, out_cap, op, count, s, err, big);
       if (CHECKED && err) {
         return 0;
       }

@@ -2,7 +2,7 @@
 """Static instruction counts of the persistent LZ window kernels, from the compiler's assembly.
 
 usage: lz_window_isa.py [--format lz4|snappy] [--commit REV] [-D...]
-       lz_window_isa.py --diff REV [--api NAME ...] [-D...]
+       lz_window_isa.py --diff REV [--api NAME ...] [--rename OLD=NEW ...] [-D...]
 
 Compiles api/<format>_api.hip for the device only with the product's flags (plus any -D given), once as it is and once
 with -DNVCOMP_LZW_RUNS=0 -- the kernel then holds only the instance of the decode loop without the run executor, the one
@@ -16,6 +16,8 @@ flags for that file plus any -D given, and compares the text of every function o
 .amdhsa_kernel descriptor, and the functions they call -- ignoring lines that hold the per-build __hip_cuid_ symbol and
 the per-file numbering of local labels. One line per function: identical, different (instructions a / b), only in REV,
 only in worktree; the exit status is 1 when any is different. This is how a refactor shows that it left the code alone.
+--rename OLD=NEW replaces OLD by NEW in REV's assembly first: a refactor that renames a kernel's parameter type renames the
+kernel's symbol (--rename 6Launch=7Tickets for lzl::Launch -> lzl::Tickets), which would otherwise read as two functions.
 """
 import argparse
 import concurrent.futures
@@ -102,6 +104,7 @@ def compile_asm(root, api, flags, out):
 def functions(asm):
     """{symbol: text} of every function; a kernel's text ends with its .amdhsa_kernel descriptor."""
     asm = "\n".join(ln for ln in asm.splitlines() if "__hip_cuid_" not in ln)
+    asm = re.sub(r"[ \t]+;", " ;", asm)  # comments are aligned behind labels, whose width follows the function's number
     asm = re.sub(r"(\.L[A-Za-z_]+|\bBB)\d+_", r"\1_", asm)  # .LBB<function number>_<block>, and BB<n>_<block> in comments
     asm = re.sub(r"(\.Lfunc_(?:begin|end))\d+", r"\1", asm)
     out = {}
@@ -118,7 +121,7 @@ def instructions(body):
     return sum(1 for ln in body.splitlines() if ln.startswith("\t") and not ln.lstrip().startswith((".", ";")) and ln.strip())
 
 
-def diff(rev, apis, extra, keep):
+def diff(rev, apis, extra, keep, renames=()):
     with tempfile.TemporaryDirectory() as tmp:
         roots = {rev: checkout(rev, tmp), "worktree": REPO}
         jobs = [(api, side) for api in apis for side in roots]
@@ -128,6 +131,8 @@ def diff(rev, apis, extra, keep):
     different = 0
     for api in apis:
         old, new = texts[api, rev], texts[api, "worktree"]
+        for a, b in (r.split("=", 1) for r in renames):
+            old = {sym.replace(a, b): text.replace(a, b) for sym, text in old.items()}
         for sym in sorted(set(old) | set(new)):
             name = subprocess.run(["c++filt", "-p", sym], stdout=subprocess.PIPE, text=True).stdout.strip()
             if sym not in new:
@@ -150,9 +155,10 @@ def main():
     ap.add_argument("--diff", default=None, metavar="REV")
     ap.add_argument("--api", nargs="+", default=["lz4_api", "snappy_api"])
     ap.add_argument("--keep", default=None, help="directory to keep the .s files in")
+    ap.add_argument("--rename", nargs="+", default=[], metavar="OLD=NEW", help="--diff: applied to REV's assembly")
     a, extra = ap.parse_known_args()
     if a.diff:
-        return diff(a.diff, a.api, extra, a.keep)
+        return diff(a.diff, a.api, extra, a.keep, a.rename)
     with tempfile.TemporaryDirectory() as tmp:
         root = checkout(a.commit, tmp)
         for label, flags in (("kernel", []), ("non_runs_loop", ["-DNVCOMP_LZW_RUNS=0"])):

@@ -441,6 +441,35 @@ def test_corrupt_streams_do_not_escape(backend, lz_path, oracle):
             assert status[i] != NvcompStatus.Success and actual[i] == 0
 
 
+def test_hand_over_streams(backend, lz_path, oracle):
+    """Streams on which the decoder changes hands in the middle of a chunk: from the chase to the streamed long literal run
+    or long match and back, a literal run before the first match, a chunk that is one literal run. liblz4 at levels 0 and
+    12; bit-exact, and a corrupt stream (flipped bytes in the middle) must fail or decode inside its slot without harm to
+    the chunk next to it."""
+    rng = np.random.RandomState(7)
+    base = datasets.text(70000, 2)
+    noise = rng.randint(0, 256, 65536).astype(np.uint8)
+    raws = [
+        base[:65536],
+        np.concatenate([base[:30000], noise[:8000], base[:20000]]),   # a literal run of 8 000 bytes in the middle
+        np.concatenate([base[:20000], np.zeros(30000, dtype=np.uint8), base[:15000]]),  # a match of 30 000 bytes in the middle
+        np.concatenate([noise[:300], base[:40000]]),                  # a literal run of 300 bytes first
+        datasets.table_rows(65536, 4),
+        noise[:65000],
+    ]
+    codec = backend.codec("LZ4")
+    for level in (0, 12):
+        comp = [oracle.ref_lz4_compress(r, level) for r in raws]
+        outs, actual, status = codec.decompress(comp, [r.size for r in raws])
+        assert (status == 0).all() and actual.tolist() == [r.size for r in raws]
+        for o, r in zip(outs, raws):
+            assert np.array_equal(o, r)
+    bad = comp[0].copy()
+    bad[5000:5040] ^= 0x5a
+    outs, actual, status = codec.decompress([bad, comp[1]], [raws[0].size, raws[1].size])
+    assert status[1] == 0 and np.array_equal(outs[1], raws[1])
+
+
 def test_batch_of_many_small_chunks(backend, oracle):
     """8 200 chunks in one launch: above the two-waves-per-chunk threshold, i.e. the persistent-wave launch as shipped
     (common/lz_launch.hip.h): every chunk must be decoded exactly once."""

@@ -32,6 +32,17 @@ __device__ __forceinline__ uint32_t steps_for(bool participates, uint32_t len)
 {
   return steps_for(wave::ballot(participates), len);
 }
+/* The same from the length classes of a batch, balloted once where the batch is prepared (gt16 = ballot(len > 16),
+ * gt8 = ballot(len > 8)): scalar only. A loop that asks once per round -- the near-match rounds -- otherwise pays the
+ * two compares every round, or, with the compares hoisted as lane booleans, a v_cndmask and a v_cmp for each to get the
+ * mask back. */
+__device__ __forceinline__ uint32_t steps_for(uint64_t participants, uint64_t gt16, uint64_t gt8)
+{
+  if (gt16 & participants) {
+    return 8;
+  }
+  return (gt8 & participants) ? 4u : 2u;
+}
 
 /* Note on alignment: a ds_read_b32 / ds_write_b32 with any misaligned lane serialises the wave instruction
  * on gfx950 (64 cycles instead of 4, scripts/microbench/lds_unaligned.hip). A variant of the copies below
@@ -76,39 +87,43 @@ __device__ __forceinline__ void copy_dwords_clamped_disjoint(uint8_t* dst, const
   }
 }
 
-/* Far-match data (registers) into the window with aligned accesses only: dst sits h = 1..4 bytes into the
- * aligned frame that starts at dst - h (h = 4: dst itself is aligned). d[] = the match's sequential dwords,
- * l4 = its last 4 bytes. Up to 3 head bytes, whole aligned dwords, up to 3 tail bytes. */
-template <uint32_t STEPS>
-__device__ __forceinline__ void far_store_aligned(uint8_t* dst, const uint32_t (&d)[8], uint32_t l4, uint32_t len, bool on)
+/* Far-match data (registers) into the window with aligned accesses only. The destination sits a = 0..3 bytes into the
+ * aligned `frame`, and the data was LOADED at source - a (execute_window_batch): d[j] is frame dword j as it
+ * stands, no realignment (loaded at the source's own address every dword took a v_alignbyte_b32: nine a batch). The match
+ * is frame bytes [a, end), end = a + len, len = kMin .. 4 * STEPS, at most 4 * STEPS + 3: dwords 0 .. STEPS - 1 can be whole
+ * ones, the bytes behind the last whole dword come from l4, the match's last 4 bytes.
+ *   head  a != 0: frame bytes [a, 4) -- all of them the match's, a match being 3 bytes at least -- as a byte (a odd) and
+ *         a 16-bit store at byte 2 (a = 1, 2): two stores at most, where byte by byte it was three;
+ *   whole dwords; dword 0 only when a = 0 (THREE: and the match has a fourth byte);
+ *   tail  end & 3 bytes: a 16-bit store (2, 3) and a byte (1, 3), out of l4's top bytes.
+ * Called by the far lanes only. */
+template <uint32_t STEPS, bool THREE>
+__device__ __forceinline__ void far_store_aligned(uint8_t* frame, uint32_t a, const uint32_t (&d)[8], uint32_t l4, uint32_t len)
 {
-  const uint32_t a = (uint32_t)((uintptr_t)dst & 3u);
-  const uint32_t h = a ? a : 4u;
-  uint8_t* frame = dst - h;
-  const uint32_t end = on ? h + len : 0u; /* frame bytes [h, end) */
-  const uint32_t sh = 4u - h;
-  const uint32_t v0 = wave::align_bytes(d[0], 0u, sh);
-#pragma unroll
-  for (uint32_t b = 1; b < 4; ++b) {
-    if (b >= h && b < end) {
-      frame[b] = (uint8_t)(v0 >> (8 * b));
-    }
+  const uint32_t end = a + len;
+  if (a & 1u) {
+    frame[a] = (uint8_t)wave::align_bytes(0u, d[0], a); /* d[0] >> 8 a */
+  }
+  if ((a + 1u) & 2u) {
+    *(uint16_t*)(frame + 2) = (uint16_t)(d[0] >> 16);
+  }
+  if (a == 0 && (!THREE || len > 3)) {
+    *(uint32_t*)frame = d[0];
   }
 #pragma unroll
-  for (uint32_t j = 1; j <= STEPS; ++j) {
-    const uint32_t v = wave::align_bytes(j < STEPS ? d[j < 8 ? j : 7] : 0u, d[j - 1], sh);
+  for (uint32_t j = 1; j < STEPS; ++j) {
     if (4 * j + 4 <= end) {
-      *(uint32_t*)(frame + 4 * j) = v;
+      *(uint32_t*)(frame + 4 * j) = d[j];
     }
   }
+  /* the last tc bytes of the match are the top tc bytes of l4 */
   const uint32_t tc = end & 3u;
   uint8_t* tp = frame + (end & ~3u);
-  const uint32_t tv = l4 >> (8 * ((4u - tc) & 3u));
-#pragma unroll
-  for (uint32_t b = 0; b < 3; ++b) {
-    if (b < tc) {
-      tp[b] = (uint8_t)(tv >> (8 * b));
-    }
+  if (tc & 2u) {
+    *(uint16_t*)tp = (uint16_t)wave::align_bytes(0u, l4, 0u - end); /* l4 >> 16 (tc = 2), l4 >> 8 (tc = 3): shift = -end & 3 */
+  }
+  if (tc & 1u) {
+    tp[tc & 2u] = (uint8_t)(l4 >> 24);
   }
 }
 

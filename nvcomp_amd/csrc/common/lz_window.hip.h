@@ -63,9 +63,6 @@ __device__ __forceinline__ void drop_front(lz::Seq& s, uint32_t take, uint32_t c
  * masked that the callers' invariant already zeroes.
  */
 
-#ifndef NVCOMP_LZW_FAR_L4_FROM_F0
-#define NVCOMP_LZW_FAR_L4_FROM_F0 0 /* A/B: the last dword of a far match of up to 16 bytes out of its first load */
-#endif
 /* A batch's whole blocks are written to HBM at its end. (Round 6 tried writing them only when the window has to slide --
  * every third or fourth batch of text, 2 KiB at a time; nothing needs them earlier: LZ4 mix 683 -> 686 GB/s, Snappy mix
  * 501 -> 484, float32 column 412 -> 400. DESIGN.md, "retired switches".) */
@@ -89,18 +86,27 @@ __device__ __forceinline__ uint32_t execute_window_batch(
     big = true;
     return 0;
   }
-  const bool mine = lane < take;
+  /* The batch's lanes as a MASK, and every predicate of the batch below as a mask too: a ballot of one compare of the
+   * sequence's own fields (the compare itself writes the mask), cut to the batch on the scalar unit. A lane takes its
+   * predicate from the mask (wave::lane_in: the mask is the exec mask of the branch). Balloted from lengths that were
+   * zeroed outside the batch first -- `mine ? len : 0` -- every one of these was an && of two lane conditions, which
+   * the compiler joins on the scalar unit and then turns into a lane boolean and back (common/lz_copy.hip.h, steps_for). */
+  const uint64_t mine_mask = take < 64 ? (1ull << take) - 1 : ~0ull;
   const uint32_t total = wave::read_lane(incl, take - 1);
   const uint32_t lit_dst = op + incl - len;
   const uint32_t match_dst = lit_dst + s.lit_len;
-  const uint32_t my_lit = mine ? s.lit_len : 0;
-  const uint32_t my_match = mine ? s.match_len : 0;
+  /* (used by lanes of the batch only) */
+  const uint32_t my_lit = s.lit_len;
+  const uint32_t my_match = s.match_len;
+  const uint64_t match_mask = wave::ballot(s.match_len != 0) & mine_mask;
+  /* the length classes, once per batch: what steps_for asks of the far store, of the literal copy and of every near round */
+  const uint64_t match_gt16 = wave::ballot(s.match_len > 16), match_gt8 = wave::ballot(s.match_len > 8);
 
   if (CHECKED) {
     /* the sums grow with the lane: the batch's end is the only output test (op <= out_cap <= 2^26, total <= kBatchMax);
      * offset 0 wraps to the largest value, so one compare covers "0 or beyond the produced output" */
     const bool bad_out = op + total > out_cap;
-    const uint64_t any_off = wave::ballot(my_match != 0) & wave::ballot(s.match_off - 1 >= match_dst);
+    const uint64_t any_off = match_mask & wave::ballot(s.match_off - 1 >= match_dst);
     if (bad_out || any_off) {
       err |= (bad_out ? lz::kErrOutput : 0u) | (any_off ? lz::kErrOffset : 0u);
       return 0;
@@ -119,27 +125,30 @@ __device__ __forceinline__ uint32_t execute_window_batch(
   /* DEFLATE (RING_LITERALS) has matches of THREE bytes -- a sixth of all matches of a zlib stream, and as whole-wave
    * copies, one after the other, they were 18 % of that decoder's time (phase clock, profiles/archive/r03_deflate_phases.json) */
   constexpr uint32_t kMinShort = RING_LITERALS ? 3 : 4;
-  const bool short_match = my_match - kMinShort <= kMatchShort - kMinShort; /* kMinShort .. kMatchShort */
-  /* the data comes with one or two 16-byte loads, which must stay inside the chunk's buffer (a source in the last 32
-   * bytes of the buffer, or a wrapped one of a corrupt unchecked stream, takes the cooperative path below) */
-  const bool far_lane = short_match && match_src + my_match <= ow.flushed && out_cap >= 32 && match_src <= out_cap - 32;
-  /* the same as masks (the compares are the ones above) */
-  const uint64_t match_mask = wave::ballot(my_match != 0);
-  const uint64_t short_mask = wave::ballot(my_match - kMinShort <= kMatchShort - kMinShort);
-  const uint64_t far_mask = out_cap >= 32 ? short_mask & wave::ballot(match_src + my_match <= ow.flushed)
-                                                & wave::ballot(match_src <= out_cap - 32)
+  /* the data comes with one or two 16-byte loads that start up to 3 bytes IN FRONT of the source -- at source - (the
+   * destination's address & 3), so that the dwords arrive as the window's aligned dwords: far_store_aligned -- and must
+   * stay inside the chunk's buffer: 3 <= match_src <= out_cap - 32 in one unsigned compare. (A source in the first 3
+   * or the last 32 bytes of the buffer, or a wrapped one of a corrupt unchecked stream, takes the cooperative path below.) */
+  const uint64_t short_mask = wave::ballot(s.match_len - kMinShort <= kMatchShort - kMinShort) & mine_mask; /* kMinShort .. kMatchShort */
+  const uint64_t far_mask = out_cap >= 35 ? short_mask & wave::ballot(match_src + s.match_len <= ow.flushed)
+                                                & wave::ballot(match_src - 3u <= out_cap - 35u)
                                           : 0ull;
-  /* (no zero fill: far_store_aligned stores nothing of a lane that is not `on`, and of a match of up to 16 bytes nothing
-   * that comes from far_data[4..7] -- the dword it may take from there is shifted out by align_bytes) */
+  const bool far_lane = wave::lane_in(far_mask);
+  /* where the destination sits in its aligned dword: the window is 16-byte aligned and wbase a multiple of 16 (out_at) */
+  const uint32_t far_a = (match_dst + ow.align) & 3u;
+  /* (no zero fill: far_store_aligned is called by the far lanes only, and of a match of up to 16 bytes it stores nothing
+   * that comes from far_data[4..7]) */
   uint32_t far_l4 = LZW_UNSET_U32;
   uint32_t far_data[8] = {LZW_UNSET_U32, LZW_UNSET_U32, LZW_UNSET_U32, LZW_UNSET_U32,
                           LZW_UNSET_U32, LZW_UNSET_U32, LZW_UNSET_U32, LZW_UNSET_U32};
-  const uint32_t far_steps = steps_for(far_mask, my_match);
+  const uint32_t far_steps = steps_for(far_mask, match_gt16, match_gt8);
   if (far_lane) {
-    const uint32_t src_at = match_src; /* (folded onto the chunk's first KiB -- L2-resident lines -- the kernel gains 4-8 %:
-                                        * profiles/r06_far_ablate.jsonl; DESIGN.md, "retired switches") */
+    /* (folded onto the chunk's first KiB -- L2-resident lines -- the kernel gains 4-8 %: profiles/r06_far_ablate.jsonl;
+     * DESIGN.md, "retired switches") */
+    const uint32_t src_at = match_src - far_a;
     /* every address is the chunk's (uniform) base plus a 32-bit lane offset: the loads take the scalar-base form, no
-     * 64-bit address is built per lane (src_at + my_match <= flushed <= out_cap < 2^31: the sums do not wrap) */
+     * 64-bit address is built per lane (3 <= match_src, match_src + my_match <= flushed <= out_cap < 2^31: the sums do
+     * not wrap) */
     const uint8_t* src = ow.out + src_at;
     /* A scattered load costs the CU's address unit a slot per lane whatever its width (profiles/archive/r02_decode_phases.json:
      * issuing 3-9 dword loads per batch was 11 % of the wave's time): 16 bytes per load, two loads at most, plus the
@@ -150,20 +159,10 @@ __device__ __forceinline__ uint32_t execute_window_batch(
       const wave::u32x4 f1 = wave::gload_u32x4(ow.out + (src_at + 16u));
       far_data[4] = f1.x, far_data[5] = f1.y, far_data[6] = f1.z, far_data[7] = f1.w;
     }
-    /* the match's last four bytes; of a three-byte match: a byte that is never used, then its three */
-#if NVCOMP_LZW_FAR_L4_FROM_F0
-    /* ... of a match of up to 16 bytes they are among the 16 bytes in hand: no third load for it */
-    if (my_match > 16) {
-      far_l4 = wave::gload_u32(src + my_match - 4);
-    } else {
-      const uint32_t d = my_match >= 4 ? my_match - 4 : 0u, k = d >> 2;
-      const uint32_t lo = k == 0 ? f0.x : k == 1 ? f0.y : k == 2 ? f0.z : f0.w;
-      const uint32_t hi = k == 0 ? f0.y : k == 1 ? f0.z : f0.w;
-      far_l4 = RING_LITERALS && my_match < 4 ? f0.x << 8 : wave::align_bytes(hi, lo, d & 3u);
-    }
-#else
-    far_l4 = RING_LITERALS && my_match < 4 ? f0.x << 8 : wave::gload_u32(ow.out + (src_at + my_match - 4u));
-#endif
+    /* the match's last four bytes; of a three-byte match: the byte in front of it (match_src >= 3), then its three.
+     * (Taken out of the first load where the match ends within it -- a select among its dwords and a shift, seven vector
+     * instructions in place of this load for those lanes -- the mix LOSES 1.7 %: profiles/ab_window_masks.jsonl, ABDE.) */
+    far_l4 = wave::gload_u32(ow.out + (match_src + my_match - 4u));
   }
 
   LZW_T(11); /* far classification + load issue */
@@ -172,16 +171,15 @@ __device__ __forceinline__ uint32_t execute_window_batch(
     uint8_t* dst = out_at(ow, lit_dst);
     /* a run of 1 .. kLitShort bytes that the ring holds is copied by its own lane (a position in front of the resident
      * range wraps to a huge value: one compare) */
-    const bool lit_own = my_lit - 1 < kLitShort && s.lit_src - ir.lo + my_lit <= ir.hi - ir.lo;
-    const bool lit_lane = lit_own && my_lit >= 4;
+    const uint64_t own_mask = wave::ballot(s.lit_len - 1 < kLitShort) & wave::ballot(s.lit_src - ir.lo + s.lit_len <= ir.hi - ir.lo) & mine_mask;
+    const uint64_t word_mask = wave::ballot(s.lit_len >= 4);
+    const bool lit_lane = wave::lane_in(own_mask & word_mask);
     /* the ring wraps at kInRing; its 16-byte mirror covers a dword that starts before the end. A run that ends inside
      * the mirror is read from ONE base address (clamped offsets added, as everywhere); only when some lane's run goes on
      * behind the mirror -- one run in a hundred -- the wave takes the loop that wraps every step's address by itself. */
-    const uint64_t own_mask = wave::ballot(my_lit - 1 < kLitShort) & wave::ballot(s.lit_src - ir.lo + my_lit <= ir.hi - ir.lo);
-    const uint64_t word_mask = wave::ballot(my_lit >= 4);
-    const uint32_t lit_steps = steps_for(own_mask & word_mask, my_lit);
+    const uint32_t lit_steps = steps_for(own_mask & word_mask, wave::ballot(s.lit_len > 16), wave::ballot(s.lit_len > 8));
     const uint32_t lit_at = s.lit_src & (kInRing - 1);
-    const uint64_t lit_wraps = wave::ballot(lit_at + my_lit > kInRing + 16) & own_mask & word_mask;
+    const uint64_t lit_wraps = wave::ballot(lit_at + s.lit_len > kInRing + 16) & own_mask & word_mask;
     if (lit_wraps == 0) {
       if (lit_lane) {
         const uint8_t* src = ir.ring + lit_at;
@@ -205,9 +203,8 @@ __device__ __forceinline__ uint32_t execute_window_batch(
     /* 1..3 bytes: byte-wise (as ONE misaligned dword store, whose excess bytes the match behind it would overwrite, they
      * measured 5 % slower on the headline: a misaligned LDS store costs a cycle or two per ACTIVE lane, and 30 % of the
      * sequences have such a run, 10 % one of four bytes or more) */
-    const bool lit_tiny = lit_own && my_lit < 4;
     if (own_mask & ~word_mask) {
-      if (lit_tiny) {
+      if (wave::lane_in(own_mask & ~word_mask)) {
         dst[0] = ir.ring[s.lit_src & (kInRing - 1)];
         if (my_lit > 1) {
           dst[1] = ir.ring[(s.lit_src + 1) & (kInRing - 1)];
@@ -218,8 +215,8 @@ __device__ __forceinline__ uint32_t execute_window_batch(
       }
     }
     LZW_T(12); /* literal runs of 1..3 bytes */
-    uint64_t pending = wave::ballot(my_lit != 0) & ~own_mask;
-    LZ_STAT("lit_lanes", wave::popc64(wave::ballot(lit_own)));
+    uint64_t pending = wave::ballot(s.lit_len != 0) & mine_mask & ~own_mask;
+    LZ_STAT("lit_lanes", wave::popc64(own_mask));
     LZ_STAT("lit_coop", wave::popc64(pending));
     while (pending) {
       const uint32_t j = wave::ctz64(pending);
@@ -242,14 +239,14 @@ __device__ __forceinline__ uint32_t execute_window_batch(
 
   LZW_T(13); /* long literal runs, whole wave */
   /* ---- far match data into the window ---- */
-  if (far_mask) {
-    uint8_t* dst = out_at(ow, far_lane ? match_dst : ow.wbase);
+  if (far_lane) {
+    uint8_t* frame = out_at(ow, match_dst - far_a);
     if (far_steps == 2) {
-      far_store_aligned<2>(dst, far_data, far_l4, my_match, far_lane);
+      far_store_aligned<2, RING_LITERALS>(frame, far_a, far_data, far_l4, my_match);
     } else if (far_steps == 4) {
-      far_store_aligned<4>(dst, far_data, far_l4, my_match, far_lane);
+      far_store_aligned<4, RING_LITERALS>(frame, far_a, far_data, far_l4, my_match);
     } else {
-      far_store_aligned<8>(dst, far_data, far_l4, my_match, far_lane);
+      far_store_aligned<8, RING_LITERALS>(frame, far_a, far_data, far_l4, my_match);
     }
   }
   wave::sync();
@@ -259,13 +256,15 @@ __device__ __forceinline__ uint32_t execute_window_batch(
   {
     /* near: a short match with a period of 4 or more whose source the window holds */
     uint64_t pending = match_mask & ~far_mask;
-    const uint64_t near_mask = match_mask & short_mask & wave::ballot(match_src >= ow.valid_lo) & wave::ballot(s.match_off >= 4);
-    LZ_STAT("match_far_lanes", wave::popc64(wave::ballot(far_lane)));
+    const uint64_t near_mask = short_mask & wave::ballot(match_src >= ow.valid_lo) & wave::ballot(s.match_off >= 4);
+    const uint32_t match_end = match_src + s.match_len; /* where a lane's source ends */
+    LZ_STAT("match_far_lanes", wave::popc64(far_mask));
     LZ_STAT("match_near_lanes", wave::popc64(near_mask));
     LZ_STAT("match_coop", wave::popc64(pending & ~near_mask));
-    LZ_STAT("match_coop_below_4", wave::popc64(wave::ballot(my_match != 0 && my_match < 4)));
-    LZ_STAT("match_coop_long", wave::popc64(wave::ballot(my_match > kMatchShort)));
-    LZ_STAT("match_coop_short_period", wave::popc64(wave::ballot(my_match != 0 && match_src >= ow.valid_lo && short_match && s.match_off < 4)));
+    LZ_STAT("match_coop_below_4", wave::popc64(match_mask & wave::ballot(my_match < 4)));
+    LZ_STAT("match_coop_long", wave::popc64(match_mask & wave::ballot(my_match > kMatchShort)));
+    LZ_STAT("match_coop_short_period",
+            wave::popc64(short_mask & wave::ballot(match_src >= ow.valid_lo) & wave::ballot(s.match_off < 4)));
     while (pending) {
       const uint32_t f = wave::ctz64(pending);
       const uint32_t hw = wave::read_lane(match_dst, f); /* every byte below hw is final */
@@ -280,12 +279,11 @@ __device__ __forceinline__ uint32_t execute_window_batch(
       }
       /* ready: a pending near lane whose source is final -- and the oldest one, whatever its source (it overlaps only
        * itself) */
-      const uint64_t ready_mask = near_mask & pending & (wave::ballot(match_src + my_match <= hw) | (1ull << f));
-      const bool ready = wave::lane_in(ready_mask);
-      const uint32_t steps = steps_for(ready_mask, my_match);
+      const uint64_t ready_mask = near_mask & pending & (wave::ballot(match_end <= hw) | (1ull << f));
+      const uint32_t steps = steps_for(ready_mask, match_gt16, match_gt8);
       LZ_STAT("mrr_rounds", 1);
       LZ_STAT("mrr_iters", steps);
-      if (ready) {
+      if (wave::lane_in(ready_mask)) {
         const uint8_t* src = out_at(ow, match_src);
         uint8_t* dst = out_at(ow, match_dst);
         if (RING_LITERALS && my_match < 4) { /* three bytes, offset >= 4 */

@@ -130,12 +130,13 @@ __device__ __forceinline__ void sched_fence()
   __builtin_amdgcn_sched_barrier(0);
 }
 
-/* Is the calling lane's bit set in the wave-uniform mask? (v_cndmask with the mask as its condition: no 1ull << lane) */
+/* Is the calling lane's bit set in the wave-uniform mask? The mask IS the lane predicate: `if (lane_in(m))` is an
+ * s_and_saveexec_b64 on m, a select takes m as its condition, and no vector instruction is spent on it. (As v_cndmask 0, 1
+ * on the mask and a compare of the result, which this was until the near-match rounds were counted, it cost two dependent
+ * vector instructions at every use.) */
 __device__ __forceinline__ bool lane_in(uint64_t mask)
 {
-  uint32_t r;
-  asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(r) : "s"(mask));
-  return r != 0;
+  return __builtin_amdgcn_inverse_ballot_w64(mask);
 }
 
 /* 64-bit mask of lanes whose predicate is true. */

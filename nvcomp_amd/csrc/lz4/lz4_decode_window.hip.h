@@ -268,11 +268,11 @@ __device__ __forceinline__ void parse(const R& r, uint32_t p, bool active, lz::S
  * longer match -- go through parse() together afterwards. (Until the middle of round 3 ONE such lane sent the whole
  * batch to parse(), which finishes a field with a second extension byte one lane after the other: every batch of a
  * sorted key column -- matches of 170 .. 680 bytes -- and the last 40 sequences of every such chunk.) */
+/* Returns the lanes whose sequence is malformed, as a mask: the persistent loop asks "any?" on the scalar unit. */
 template <class R>
-__device__ __forceinline__ void parse_batch(const R& r, uint32_t p, uint32_t from, uint32_t to, lz::Seq& s, bool& bad)
+__device__ __forceinline__ uint64_t parse_batch_mask(const R& r, uint32_t p, uint32_t from, uint32_t to, lz::Seq& s)
 {
   const uint32_t lane = (uint32_t)wave::lane_id();
-  const bool active = lane - from < to - from;
   const uint32_t lim = r.hi < r.vend ? r.hi : r.vend;
   const uint64_t w = ring_bytes8(r, p); /* a lane outside [from, to) reads somewhere inside the ring: harmless */
   const uint32_t t = (uint32_t)w & 0xffu;
@@ -291,25 +291,32 @@ __device__ __forceinline__ void parse_batch(const R& r, uint32_t p, uint32_t fro
    * set), a seventh of the match length, fields that are not resident or reach the end of the chunk (q + 8 < vend also
    * says that a token follows the match) */
   const bool lit2 = ((uint32_t)w & 0xfff0u) == 0xfff0u;
-  const bool straight = !lit2 && n255 < 6 && p >= r.lo && q + 8 < lim;
-  const bool mine = active && straight;
+  /* (masks of single compares joined on the scalar unit, the lane's predicate taken from the mask: common/lz_copy.hip.h,
+   * steps_for; common/lz_window.hip.h) */
+  const uint64_t active = wave::ballot(lane - from < to - from);
+  const uint64_t other = wave::ballot(lit2) | wave::ballot(n255 >= 6) | wave::ballot(p < r.lo) | wave::ballot(q + 8 >= lim);
+  const bool mine = wave::lane_in(active & ~other);
   s.lit_src = mine ? lit_src : 0;
   s.lit_len = mine ? lit : 0;
   s.match_off = mine ? ((uint32_t)x & 0xffffu) : 0;
   s.match_len = mine ? mcode + 4 + (mcode == 15 ? mext : 0u) : 0;
-  bad = false;
-  /* (a mask of single compares joined on the scalar unit: common/lz_copy.hip.h, steps_for) */
-  const uint64_t rest = wave::ballot(lane - from < to - from)
-                        & (wave::ballot(lit2) | wave::ballot(n255 >= 6) | wave::ballot(p < r.lo) | wave::ballot(q + 8 >= lim));
+  const uint64_t rest = active & other;
+  uint64_t bad_mask = 0;
   if (rest) {
     lz::Seq g;
     bool gbad;
     parse(r, p, wave::lane_in(rest), g, gbad);
     if (wave::lane_in(rest)) {
       s = g;
-      bad = gbad;
     }
+    bad_mask = wave::ballot(gbad) & rest;
   }
+  return bad_mask;
+}
+template <class R>
+__device__ __forceinline__ void parse_batch(const R& r, uint32_t p, uint32_t from, uint32_t to, lz::Seq& s, bool& bad)
+{
+  bad = wave::lane_in(parse_batch_mask(r, p, from, to, s));
 }
 
 /* What the workgroup-per-chunk decoder (common/lz_team.hip.h) and the two-wave decoder (common/lz_pair.hip.h) need to know
@@ -412,13 +419,12 @@ __device__ __forceinline__ uint32_t decode_chunk(
     }
     if (refill) {
       lz::Seq fresh;
-      bool bad;
-      parse_batch(ir, seqpos, before, count, fresh, bad);
+      const uint64_t bad = parse_batch_mask(ir, seqpos, before, count, fresh);
       LZW_T(3);
       if (lane >= before) {
         s = fresh;
       }
-      if (wave::ballot(bad)) {
+      if (bad) {
         err |= lz::kErrInput;
         return 0;
       }

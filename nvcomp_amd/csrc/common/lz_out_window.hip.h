@@ -39,15 +39,18 @@ __device__ __forceinline__ uint8_t* out_at(const OutWindow& w, uint32_t pos)
 
 /* Slide the window so that the batch's `need` bytes (at most kBatchMax) fit after position op. (Until round 6 it made room for
  * kBatchMax whatever the batch produced, i.e. slid in front of every batch: a batch of text is ~700 bytes, the slide two
- * syncs and a copy: profiles/r06_ab_runs.jsonl, "roomk". What stays behind without a slide is history: a match into
- * it is an LDS copy instead of a load from memory.) */
+ * syncs and a copy: profiles/r06_ab_runs.jsonl, "roomk".) What stays behind without a slide -- up to 1.4 KiB of flushed
+ * output -- is history: execute_window_batch copies a short match whose whole source lies in [valid_lo, flushed) in LDS
+ * instead of fetching it (a twelfth of the mix's far matches: scripts/window_history_model.py). */
 __device__ __forceinline__ void out_make_room(OutWindow& w, uint32_t op, uint32_t need)
 {
   if (op - w.wbase + w.align + need <= kOutWin) {
     return;
   }
-  /* history kept: kKeep bytes (as much as the batch leaves room for, up to 256 / 512 / 960 bytes: no gain,
-   * profiles/r06_ab_runs.jsonl r6ax) */
+  /* history kept: kKeep bytes. (As much as the coming batch leaves room for, up to 64 .. 1 024 bytes or all of it, with the
+   * matches into it copied in LDS: more slides and longer ones cost more than the requests they save, LZ4 mix 726 GB/s
+   * with 32 bytes, 721 with 512, 709 with 1 024, 692 with all that fits: profiles/ab_window_history.jsonl. The round-6
+   * measurement of the same, r6ax, could not see history at all: every flushed source was fetched then.) */
   uint32_t keep_from = op > kKeep ? op - kKeep : 0;
   if (keep_from > w.flushed) {
     keep_from = w.flushed; /* the tail that waits for its 16-byte block to fill up always stays (kKeep < 16: no history at all) */

@@ -66,7 +66,8 @@ __device__ __forceinline__ void drop_front(lz::Seq& s, uint32_t take, uint32_t c
 /* A batch's whole blocks are written to HBM at its end. (Round 6 tried writing them only when the window has to slide --
  * every third or fourth batch of text, 2 KiB at a time; nothing needs them earlier: LZ4 mix 683 -> 686 GB/s, Snappy mix
  * 501 -> 484, float32 column 412 -> 400. DESIGN.md, "retired switches".) */
-template <bool CHECKED, bool RING_LITERALS = false>
+/* HISTORY: a short match whose whole source the window still holds is copied in LDS, not fetched (below). */
+template <bool CHECKED, bool RING_LITERALS = false, bool HISTORY = false>
 __device__ __forceinline__ uint32_t execute_window_batch(
     InRing& ir, OutWindow& ow, uint32_t out_cap, uint32_t& op, uint32_t n, const lz::Seq& s, uint32_t& err, bool& big)
 {
@@ -130,9 +131,21 @@ __device__ __forceinline__ uint32_t execute_window_batch(
    * stay inside the chunk's buffer: 3 <= match_src <= out_cap - 32 in one unsigned compare. (A source in the first 3
    * or the last 32 bytes of the buffer, or a wrapped one of a corrupt unchecked stream, takes the cooperative path below.) */
   const uint64_t short_mask = wave::ballot(s.match_len - kMinShort <= kMatchShort - kMinShort) & mine_mask; /* kMinShort .. kMatchShort */
-  const uint64_t far_mask = out_cap >= 35 ? short_mask & wave::ballot(match_src + s.match_len <= ow.flushed)
-                                                & wave::ballot(match_src - 3u <= out_cap - 35u)
-                                          : 0ull;
+  /* near: a short match with a period of 4 or more whose source STARTS in what the window holds, [valid_lo, op): copied
+   * in LDS by its own lane, in the rounds below */
+  const uint64_t near_mask = short_mask & wave::ballot(match_src >= ow.valid_lo) & wave::ballot(s.match_off >= 4);
+  /* A source that is flushed to its end is final, and in the output buffer. With HISTORY, where the window holds all of it
+   * as well -- the 32 bytes a slide kept and whatever the batches since have added, up to 1.4 KiB (out_make_room) -- the
+   * match is a near one that is ready in the first round, and costs no memory request: only the others are far. (A source
+   * that straddles valid_lo starts in front of it: far.) That is a twelfth of the LZ4 mix's far matches and a fifth of
+   * the Snappy mix's (scripts/window_history_model.py, scripts/emu_match_rounds.py), and it pays only where the card's
+   * gather rate is what bounds the launch -- the one-wave LZ4 kernel on 65 536 chunks of the mix, 714 -> 728 GB/s: for a
+   * wave that waits for its other far loads anyway, the copy in LDS is work on top. Snappy mix 547 -> 520 GB/s, 4 096 chunks
+   * of the LZ4 mix (two waves a chunk) 388 -> 373, the same with these matches copied beside the far store instead of
+   * in the rounds: profiles/ab_window_history.jsonl. So the decoders say which they are. */
+  const uint64_t final_mask = short_mask & wave::ballot(match_src + s.match_len <= ow.flushed);
+  const uint64_t hist_mask = HISTORY ? final_mask & near_mask : 0ull;
+  const uint64_t far_mask = out_cap >= 35 ? final_mask & ~hist_mask & wave::ballot(match_src - 3u <= out_cap - 35u) : 0ull;
   const bool far_lane = wave::lane_in(far_mask);
   /* where the destination sits in its aligned dword: the window is 16-byte aligned and wbase a multiple of 16 (out_at) */
   const uint32_t far_a = (match_dst + ow.align) & 3u;
@@ -254,12 +267,11 @@ __device__ __forceinline__ uint32_t execute_window_batch(
 
   /* ---- remaining matches, oldest first: multi-round resolution in LDS ---- */
   {
-    /* near: a short match with a period of 4 or more whose source the window holds */
     uint64_t pending = match_mask & ~far_mask;
-    const uint64_t near_mask = short_mask & wave::ballot(match_src >= ow.valid_lo) & wave::ballot(s.match_off >= 4);
     const uint32_t match_end = match_src + s.match_len; /* where a lane's source ends */
     LZ_STAT("match_far_lanes", wave::popc64(far_mask));
     LZ_STAT("match_near_lanes", wave::popc64(near_mask));
+    LZ_STAT("match_hist_lanes", wave::popc64(hist_mask));
     LZ_STAT("match_coop", wave::popc64(pending & ~near_mask));
     LZ_STAT("match_coop_below_4", wave::popc64(match_mask & wave::ballot(my_match < 4)));
     LZ_STAT("match_coop_long", wave::popc64(match_mask & wave::ballot(my_match > kMatchShort)));

@@ -439,7 +439,7 @@ __device__ __forceinline__ uint32_t decode_chunk(
       gate = wave::uniform(lzw::run_gate_tried(gate, take, misfit));
     }
     if (take == 0) {
-      take = lzw::execute_window_batch<CHECKED, false>(ir, ow, out_cap, op, count, s, err, big);
+      take = lzw::execute_window_batch<CHECKED, false, true>(ir, ow, out_cap, op, count, s, err, big); /* HISTORY: one wave a chunk is what runs at the card's gather rate */
       if (CHECKED && err) {
         return 0;
       }

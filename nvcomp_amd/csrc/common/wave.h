@@ -145,7 +145,7 @@ __device__ __forceinline__ uint64_t ballot(bool pred)
   return __builtin_amdgcn_ballot_w64(pred);
 }
 
-/* Value of lane `lane` (wave-uniform index) broadcast to the scalar unit. */
+/* Value of lane `lane` (wave-uniform index, 0 ... 63) broadcast to the scalar unit. */
 __device__ __forceinline__ uint32_t read_lane(uint32_t v, uint32_t lane)
 {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
@@ -190,7 +190,7 @@ __device__ __forceinline__ const WAVE_CONSTANT T* kernel_args(const T& first_par
   return (const WAVE_CONSTANT T*)p;
 }
 
-/* `vec` with lane `lane` (wave-uniform) replaced by the uniform value `val`. */
+/* `vec` with lane `lane` (wave-uniform, 0 ... 63) replaced by the uniform value `val`. */
 __device__ __forceinline__ uint32_t write_lane(uint32_t vec, uint32_t val, uint32_t lane)
 {
   return ((uint32_t)lane_id() == lane) ? val : vec;
@@ -212,7 +212,9 @@ __device__ __forceinline__ uint32_t write_lane_scalar(uint32_t vec, uint32_t val
  * path of the LZ decoders (one iteration per token), so it is written out: 2 VALU
  * (v_readlane, v_writelane) + 4 SALU per iteration, the lane counter living in M0. The
  * CU's single scalar ALU is the resource the decoders run out of first.
- * Requires k + (iterations) <= 64. r and k are updated in place.
+ * Requires k + (iterations) <= 64, and step >= 1 in every lane the chain visits: with a step of 0 the walk does not end. The
+ * last step may lead anywhere at or above limit (r is not clamped). r and k are updated in place; lanes of rec the walk did
+ * not write keep their value.
  */
 __device__ __forceinline__ void chain_walk(uint32_t step, uint32_t limit, uint32_t& r, uint32_t& k, uint32_t& rec)
 {
@@ -236,7 +238,9 @@ __device__ __forceinline__ void chain_walk(uint32_t step, uint32_t limit, uint32
 /*
  * Greedy walk over a mask of candidate lanes, each with a length below 64 in `len`: from lane `start` (< 64, and at least
  * one candidate at or above it) repeat { f = the lowest candidate at or above the current lane; take it; go on at
- * f + len[f] }. Returns the taken lanes in `taken` and where the walk stopped (f + len[f] of the last one taken) in `end`.
+ * f + len[f] }. Returns the taken lanes in `taken` and where the walk stopped (f + len[f] of the last one taken, which may
+ * lie above 64) in `end`. Every lane the walk takes needs a length of 1 ... 63: with a length of 0 the same lane is taken
+ * again and again and the walk does not end. The length of a lane that is not taken is never read.
  * The serial part of the LZ compressors' match selection, one iteration per selected match, written out: 7 SALU + 1 VALU
  * an iteration (the compiler's version of the same loop: 16).
  */
@@ -467,7 +471,8 @@ __device__ __forceinline__ uint32_t align_bits(uint32_t hi, uint32_t lo, uint32_
   return __builtin_amdgcn_alignbit(hi, lo, shift);
 }
 
-/* Bytes [shift, shift + 4) of the 8-byte value hi:lo, shift in 0..3 (v_alignbyte_b32). */
+/* Bytes [shift, shift + 4) of the 8-byte value hi:lo, shift in 0..3 (v_alignbyte_b32). Only the low two bits of the shift
+ * count: any other value acts as shift & 3, which common/lz_copy.hip.h relies on (tests/test_wave_primitives.py pins it). */
 __device__ __forceinline__ uint32_t align_bytes(uint32_t hi, uint32_t lo, uint32_t shift)
 {
   return __builtin_amdgcn_alignbyte(hi, lo, shift);
@@ -489,7 +494,9 @@ __device__ __forceinline__ uint32_t bit_reverse(uint32_t v)
   return __builtin_bitreverse32(v);
 }
 
-/* Byte permute (v_perm_b32): result byte i = byte sel[i] of the 8-byte value hi:lo (0-3 = lo, 4-7 = hi). */
+/* Byte permute (v_perm_b32): result byte i = byte sel[i] of the 8-byte value hi:lo (0-3 = lo, 4-7 = hi); a selector byte
+ * of 12 gives 0x00 and 13 ... 255 give 0xff. Selector bytes 8 ... 11 (sign replication on the card) are not part of the
+ * contract: the host emulation refuses them. */
 __device__ __forceinline__ uint32_t perm_bytes(uint32_t hi, uint32_t lo, uint32_t sel)
 {
   return __builtin_amdgcn_perm(hi, lo, sel);

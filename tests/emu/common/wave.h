@@ -304,12 +304,18 @@ inline uint32_t bit_reverse(uint32_t v)
   return __builtin_bswap32(v);
 }
 
+/* Selector bytes 0-7 pick a byte of hi:lo, 12 is 0x00 and 13-255 are 0xff. 8-11 replicate a sign bit on the card; no
+ * caller uses them and they are outside the contract (tests/wave_model.py: perm_bytes), so they are refused here. */
 inline uint32_t perm_bytes(uint32_t hi, uint32_t lo, uint32_t sel)
 {
   const uint64_t v = ((uint64_t)hi << 32) | lo;
   uint32_t r = 0;
   for (int i = 0; i < 4; ++i) {
     const uint32_t k = (sel >> (8 * i)) & 0xffu;
+    if (k >= 8 && k <= 11) {
+      fprintf(stderr, "emu: perm_bytes with a selector byte in 8..11\n");
+      abort();
+    }
     const uint32_t b = k < 8 ? (uint32_t)(v >> (8 * k)) & 0xffu : k == 12 ? 0u : 0xffu;
     r |= b << (8 * i);
   }

@@ -24,6 +24,7 @@ using ::wave::reduce_add;
 using ::wave::reduce_max;
 using ::wave::scan_add_inclusive;
 using ::wave::sync;
+using ::wave::umax;
 using ::wave::uniform;
 
 } // namespace wave

@@ -107,43 +107,11 @@ __device__ __forceinline__ void compress_one_chunk(
     }
     return;
   }
-  const uint32_t num_sub = (n_bytes + p.sub_bytes - 1) / p.sub_bytes;
-  if (lane == 0) {
-    uint32_t* h = (uint32_t*)dst;
-    h[0] = casc::kMagic;
-    h[1] = p.type | (p.num_rles << 8) | (p.num_deltas << 16) | ((p.use_bp ? 1u : 0u) << 24);
-    h[2] = n_bytes;
-    h[3] = p.sub_bytes;
-    h[4] = num_sub;
-  }
-  uint32_t* table = (uint32_t*)(dst + kHeaderBytes);
-  uint8_t* payload = dst + kHeaderBytes + 4 * (size_t)num_sub;
-  uint8_t* slice = lds + (size_t)wv * lds_per_wave;
-  uint32_t pay = 0;
-  bool deferred = false;
-  for (uint32_t s = 0; s < num_sub; ++s) {
-    const uint32_t off = s * p.sub_bytes;
-    const uint32_t bytes = n_bytes - off < p.sub_bytes ? n_bytes - off : p.sub_bytes;
-    uint32_t sz;
-    switch (w) {
-    case 1: sz = casc::compress_sub<uint8_t>(src + off, bytes, payload + pay, p, slice, lds_per_wave); break;
-    case 2: sz = casc::compress_sub<uint16_t>(src + off, bytes, payload + pay, p, slice, lds_per_wave); break;
-    case 4: sz = casc::compress_sub<uint32_t>(src + off, bytes, payload + pay, p, slice, lds_per_wave); break;
-    default: sz = casc::compress_sub<uint64_t>(src + off, bytes, payload + pay, p, slice, lds_per_wave); break;
-    }
-    if (sz == casc::kSubNeedsLds) {
-      deferred = true; /* the whole chunk is compressed again by the next pass; the host sized the last pass for the worst case */
-      LZ_STAT("casc_compress_chunks_deferred", 1);
-      LZ_STAT("casc_compress_subs_wasted", s);
-      break;
-    }
-    LZ_STAT("casc_compress_subs", 1);
-    pay += sz;
-    if (lane == 0) {
-      table[s] = pay;
-    }
-    wave::sync();
-  }
+  /* header, sub-chunk table and payloads: the core's. A chunk it defers is compressed again, whole, by the next pass; the host
+   * sized the last pass for the worst case */
+  const casc::CompressedChunk done = casc::compress_chunk(src, n_bytes, dst, p, lds + (size_t)wv * lds_per_wave, lds_per_wave, lane);
+  const bool deferred = done.deferred;
+  const uint32_t num_sub = done.num_sub, pay = done.pay;
   if (lane == 0) {
     if (deferred && pass < last_pass) {
       todo[chunk] = pass + 1;
@@ -239,114 +207,13 @@ __device__ __forceinline__ void decode_one_chunk(
   uint8_t* dst = wave::uniform_ptr((uint8_t*)out_ptrs[chunk]);
   const size_t src_len = wave::uniform64(comp_bytes[chunk]);
   const size_t cap = wave::uniform64(out_caps[chunk]);
-  uint32_t err = casc::kOk;
-  uint32_t produced = 0;
-  bool deferred = false;
-  do {
-    if (((uintptr_t)src & 3u) != 0) {
-      err = casc::kErrAlign;
-      break;
-    }
-    if (src_len < kHeaderBytes) {
-      err = casc::kErrInput;
-      break;
-    }
-    const uint32_t* h = (const uint32_t*)src;
-    const uint32_t magic = wave::uniform(h[0]);
-    const uint32_t cfg = wave::uniform(h[1]);
-    const uint32_t n_bytes = wave::uniform(h[2]);
-    const uint32_t sub = wave::uniform(h[3]);
-    const uint32_t num_sub = wave::uniform(h[4]);
-    const uint32_t type = cfg & 0xffu, num_rles = (cfg >> 8) & 0xffu, num_deltas = (cfg >> 16) & 0xffu;
-    if (magic != casc::kMagic || type > 7 || num_rles > 7 || num_deltas > 7) {
-      err = casc::kErrInput;
-      break;
-    }
-    const uint32_t w = casc::type_width(type);
-    if (sub == 0 || sub % w != 0 || n_bytes % w != 0 || sub / w > casc::kMaxElems
-        || num_sub != (uint32_t)(((uint64_t)n_bytes + sub - 1) / sub) || src_len < kHeaderBytes + 4 * (uint64_t)num_sub) {
-      err = casc::kErrInput;
-      break;
-    }
-    if (n_bytes > cap) {
-      err = casc::kErrOutput;
-      break;
-    }
-    if (((uintptr_t)dst & (w - 1)) != 0) {
-      err = casc::kErrAlign;
-      break;
-    }
-    const uint32_t* table = (const uint32_t*)(src + kHeaderBytes);
-    const uint8_t* payload = src + kHeaderBytes + 4 * (size_t)num_sub;
-    const uint32_t pay_len = (uint32_t)(src_len - kHeaderBytes - 4 * (size_t)num_sub);
-    uint8_t* slice = lds + (size_t)wv * lds_per_wave;
-    /* The sub-chunk table is read 64 entries at a time (one coalesced load, then v_readlane), and the first
-     * 256 bytes of the wave's NEXT sub-chunk -- all of its header words -- are requested before the current one is
-     * decoded: per sub-chunk one memory round trip is exposed (the packed words) instead of three. */
-    uint32_t tab = 0, tab_base = 0xffffffffu;
-    auto table_at = [&](uint32_t i) -> uint32_t { /* table[i], i < num_sub (uniform) */
-      if ((i & ~63u) != tab_base) {
-        tab_base = i & ~63u;
-        tab = tab_base + lane < num_sub ? table[tab_base + lane] : 0u;
-      }
-      return wave::read_lane(tab, i & 63u);
-    };
-    auto load_head = [&](uint32_t b, uint32_t e) -> uint32_t {
-      const uint32_t lim = e < pay_len ? e : pay_len;
-      return (b <= lim && 4 * lane + 4 <= lim - b) ? *(const uint32_t*)(payload + b + 4 * lane) : 0u;
-    };
-    uint32_t begin = 0, end = 0, head = 0;
-    if (first_sub < num_sub) {
-      begin = first_sub ? table_at(first_sub - 1) : 0u;
-      end = table_at(first_sub);
-      head = load_head(begin, end);
-    }
-    for (uint32_t s = first_sub; s < num_sub && !err && !deferred; s += sub_stride) {
-      const uint32_t off = s * sub;
-      const uint32_t bytes = n_bytes - off < sub ? n_bytes - off : sub;
-      if (end < begin || end > pay_len || end - begin < 4) {
-        err = casc::kErrInput;
-        break;
-      }
-      uint32_t next_begin = 0, next_end = 0, next_head = 0;
-      if (s + sub_stride < num_sub) {
-        next_begin = table_at(s + sub_stride - 1);
-        next_end = table_at(s + sub_stride);
-        next_head = load_head(next_begin, next_end);
-      }
-      uint32_t rc;
-      switch (w) {
-      case 1:
-        rc = casc::decompress_sub<uint8_t>(payload + begin, end - begin, head, dst + off, bytes, num_rles, num_deltas, slice, lds_per_wave);
-        break;
-      case 2:
-        rc = casc::decompress_sub<uint16_t>(payload + begin, end - begin, head, dst + off, bytes, num_rles, num_deltas, slice, lds_per_wave);
-        break;
-      case 4:
-        rc = casc::decompress_sub<uint32_t>(payload + begin, end - begin, head, dst + off, bytes, num_rles, num_deltas, slice, lds_per_wave);
-        break;
-      default:
-        rc = casc::decompress_sub<uint64_t>(payload + begin, end - begin, head, dst + off, bytes, num_rles, num_deltas, slice, lds_per_wave);
-        break;
-      }
-      LZ_STAT("casc_decompress_subs", 1);
-      if (rc == casc::kSubNeedLds) {
-        LZ_STAT("casc_decompress_subs_deferred", 1);
-        if (pass < 2) {
-          deferred = true; /* whatever was already written is decoded again by the next pass */
-        } else {
-          err = casc::kErrInput; /* larger than anything the compressor accepts */
-        }
-      } else if (rc != casc::kSubOk) {
-        err = casc::kErrInput;
-      }
-      begin = next_begin;
-      end = next_end;
-      head = next_head;
-      wave::sync();
-    }
-    produced = n_bytes;
-  } while (false);
+  /* the header checks, the sub-chunk table and this wave's share of the sub-chunks: the core's. Before the last pass a
+   * sub-chunk whose streams do not fit the slice hands the chunk on; in the last pass it is larger than anything the
+   * compressor accepts */
+  const casc::DecodedChunk done = casc::decode_chunk(src, src_len, dst, cap, first_sub, sub_stride, lane, lds + (size_t)wv * lds_per_wave,
+                                                    lds_per_wave, pass < 2);
+  const uint32_t err = done.err, produced = done.produced;
+  const bool deferred = done.deferred;
   if (team) {
     if (lane == 0 && (err || deferred)) {
       atomicOr(verdict + 0, err);
@@ -634,6 +501,6 @@ NVCOMP_API_DECOMPRESS_TEMP_SIZE_EX(Cascaded)
 /* Profiling builds only: read (and clear) the per-phase cycle sums of the Cascaded decoder. */
 extern "C" int nvcompAmdCascProfRead(unsigned long long* host_slots, int n)
 {
-  return prof_read_and_clear<casc::kProfSlots, 64>(casc::g_prof, host_slots, n); /* 64 copies of every slot */
+  return prof_read_and_clear<casc_prof::kProfSlots, 64>(casc_prof::g_prof, host_slots, n); /* 64 copies of every slot */
 }
 #endif

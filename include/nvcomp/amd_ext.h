@@ -32,6 +32,35 @@ nvcompStatus_t nvcompAmdBatchedPackAsync(
     size_t* device_offsets,
     hipStream_t stream);
 
+/* Inspection entries for tests and scripts, not needed by any caller of the batched API. `resident_places` receives the
+ * number of chunks a persistent one-wave LZ4 / Snappy decode launch keeps in flight on the current device (0 when the
+ * runtime cannot tell). Where `order_offset` is not NULL, the pass that orders such a launch's last places by compressed
+ * size runs alone on `stream`, over the two size arrays of a decompress call, with the places in front of `first_ordered`
+ * left to their own chunks: *order_offset is then the offset in `device_temp_ptr` of batch_size chunk indices (uint32),
+ * and the first word of the buffer, the launch's ticket, is cleared. nvcompErrorInvalidValue when the buffer is NULL, not
+ * 4-byte aligned or too small (16 + 4 x batch_size + 768 bytes for every 1 024 chunks, 64 times at the most), or
+ * first_ordered > batch_size. Either result pointer may be NULL. */
+nvcompStatus_t nvcompAmdLZ4DecompressOrderAsync(
+    const size_t* device_compressed_bytes,
+    const size_t* device_uncompressed_bytes,
+    size_t first_ordered,
+    size_t batch_size,
+    void* device_temp_ptr,
+    size_t temp_bytes,
+    size_t* order_offset,
+    size_t* resident_places,
+    hipStream_t stream);
+nvcompStatus_t nvcompAmdSnappyDecompressOrderAsync(
+    const size_t* device_compressed_bytes,
+    const size_t* device_uncompressed_bytes,
+    size_t first_ordered,
+    size_t batch_size,
+    void* device_temp_ptr,
+    size_t temp_bytes,
+    size_t* order_offset,
+    size_t* resident_places,
+    hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 
 #include <stdlib.h>
 
+#include "nvcomp/amd_ext.h"
 #include "nvcomp/lz4.h"
 
 #include "common/lz_api.hip.h"
@@ -127,8 +128,8 @@ extern "C" {
 nvcompStatus_t nvcompBatchedLZ4DecompressGetTempSize(
     size_t num_chunks, size_t /*max_uncompressed_chunk_bytes*/, size_t* temp_bytes)
 {
-  /* the ticket counter of the persistent waves / workgroups (common/lz_launch.hip.h) */
-  return lzl::temp_size(num_chunks, temp_bytes, lzl::kTicketBytes);
+  /* the ticket counter of the persistent waves / workgroups (common/lz_launch.hip.h) and the order they hand out in */
+  return lzl::temp_size(num_chunks, temp_bytes, lzl::order_query_bytes(num_chunks));
 }
 
 NVCOMP_API_DECOMPRESS_TEMP_SIZE_EX(LZ4)
@@ -149,6 +150,15 @@ nvcompStatus_t nvcompBatchedLZ4DecompressAsync(
                                lz4_decompress_pair_kernel<true>, lz4_decompress_window_kernel<true>>(
       "LZ4", device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
       device_actual_uncompressed_bytes, batch_size, device_temp_ptr, temp_bytes, device_uncompressed_ptrs, device_statuses, stream);
+}
+
+nvcompStatus_t nvcompAmdLZ4DecompressOrderAsync(
+    const size_t* device_compressed_bytes, const size_t* device_uncompressed_bytes, size_t first_ordered, size_t batch_size,
+    void* device_temp_ptr, size_t temp_bytes, size_t* order_offset, size_t* resident_places, hipStream_t stream)
+{
+  return lzl::order_inspect_async<lz4_decompress_window_kernel<true>>(
+      device_compressed_bytes, device_uncompressed_bytes, first_ordered, batch_size, device_temp_ptr, temp_bytes, order_offset,
+      resident_places, stream);
 }
 
 nvcompStatus_t nvcompBatchedLZ4GetDecompressSizeAsync(

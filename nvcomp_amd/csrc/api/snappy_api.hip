@@ -122,9 +122,9 @@ extern "C" {
 nvcompStatus_t nvcompBatchedSnappyDecompressGetTempSize(
     size_t num_chunks, size_t /*max_uncompressed_chunk_bytes*/, size_t* temp_bytes)
 {
-  /* the ticket counter of the persistent waves / workgroups (common/lz_launch.hip.h); the decoder itself keeps all state in
-   * registers and LDS */
-  return lzl::temp_size(num_chunks, temp_bytes);
+  /* the ticket counter of the persistent waves / workgroups (common/lz_launch.hip.h) and the order they hand out in; the
+   * decoder itself keeps all state in registers and LDS */
+  return lzl::temp_size(num_chunks, temp_bytes, lzl::order_query_bytes(num_chunks));
 }
 
 NVCOMP_API_DECOMPRESS_TEMP_SIZE_EX(Snappy)
@@ -145,6 +145,15 @@ nvcompStatus_t nvcompBatchedSnappyDecompressAsync(
                                snappy_decompress_pair_kernel<true>, snappy_decompress_window_kernel<true>>(
       "Snappy", device_compressed_ptrs, device_compressed_bytes, device_uncompressed_bytes,
       device_actual_uncompressed_bytes, batch_size, device_temp_ptr, temp_bytes, device_uncompressed_ptrs, device_statuses, stream);
+}
+
+nvcompStatus_t nvcompAmdSnappyDecompressOrderAsync(
+    const size_t* device_compressed_bytes, const size_t* device_uncompressed_bytes, size_t first_ordered, size_t batch_size,
+    void* device_temp_ptr, size_t temp_bytes, size_t* order_offset, size_t* resident_places, hipStream_t stream)
+{
+  return lzl::order_inspect_async<snappy_decompress_window_kernel<true>>(
+      device_compressed_bytes, device_uncompressed_bytes, first_ordered, batch_size, device_temp_ptr, temp_bytes, order_offset,
+      resident_places, stream);
 }
 
 nvcompStatus_t nvcompBatchedSnappyGetDecompressSizeAsync(

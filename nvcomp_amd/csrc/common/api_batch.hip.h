@@ -39,13 +39,15 @@ struct Batch
   int* statuses; /* nvcompStatus_t* */
 };
 
-/* The head of a persistent kernel's single parameter: the batch, the ticket counter (NULL: one chunk per wave, statically)
- * and the first chunk index handed out by ticket (= waves of the launch). Read through wave::kernel_args where needed. */
+/* The head of a persistent kernel's single parameter: the batch, the ticket counter (NULL: one chunk per wave, statically),
+ * the first place handed out by ticket (= waves of the launch) and, for the kernels that read it, the chunk of every
+ * place (common/lz_order.hip.h; NULL: place i is chunk i). Read through wave::kernel_args where needed. */
 struct Tickets
 {
   Batch b;
   uint32_t* ticket;
   size_t first_dynamic;
+  const uint32_t* order;
 };
 
 /* The wave's next chunk: `first_dynamic` + a ticket (lane 0 draws it, the wave shares it). */
@@ -203,6 +205,14 @@ struct ResidentCache
   }
 };
 
+/* ... of Kernel, whoever asks. */
+template <auto Kernel>
+static inline unsigned resident_fit(unsigned block_threads, int max_per_cu)
+{
+  static ResidentCache resident; /* per kernel; inside, per device ordinal */
+  return resident.get(Kernel, block_threads, max_per_cu);
+}
+
 /* Launch Kernel over a batch, `places` chunks per workgroup at a time. Persistent when the caller's temp buffer
  * can hold the ticket counter: as many workgroups as stay resident (at most `max_per_cu` per CU; 0: no cap), the rest of
  * the batch by ticket. Otherwise one place per chunk, statically. make_args(ticket, first_dynamic) -> the kernel's parameter. */
@@ -214,8 +224,7 @@ static inline void launch_persistent(
   unsigned groups = (unsigned)((batch_size + places - 1) / places);
   uint32_t* ticket = nullptr;
   if (temp != nullptr && temp_bytes >= sizeof(uint32_t) && ((uintptr_t)temp & 3u) == 0) {
-    static ResidentCache resident; /* per kernel; inside, per device ordinal */
-    const unsigned fit = resident.get(Kernel, block_threads, max_per_cu);
+    const unsigned fit = resident_fit<Kernel>(block_threads, max_per_cu);
     if (fit != 0 && fit < groups && hipMemsetAsync(temp, 0, sizeof(uint32_t), stream) == hipSuccess) {
       ticket = (uint32_t*)temp;
       groups = fit;

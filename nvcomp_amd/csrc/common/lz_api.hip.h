@@ -18,6 +18,7 @@
 
 #include "common/log.h"
 #include "common/lz_launch.hip.h"
+#include "common/lz_order.hip.h"
 #include "common/lz_window.hip.h"
 #include "common/lz_pair.hip.h"
 #include "common/lz_team.hip.h"
@@ -42,8 +43,13 @@ namespace lzl {
 constexpr unsigned kDecWaves = NVCOMP_LZ_DEC_WAVES_PER_BLOCK;
 constexpr unsigned kEncWaves = NVCOMP_LZM_WAVES_PER_BLOCK; /* the compressors' workgroup size */
 constexpr unsigned kWideWaves = NVCOMP_LZMW_WAVES_PER_BLOCK;
+/* the size query's threshold is the waves of a whole MI355X (256 CUs) at the launch's cap: change them together */
+static_assert(NVCOMP_LZ_MAX_WG_PER_CU == 0 || kOrderMinQueryBatch == 256u * NVCOMP_LZ_MAX_WG_PER_CU * kDecWaves,
+              "common/lz_order.hip.h: kOrderMinQueryBatch is the resident waves of the one-wave decoders");
 
 /* One wave (`w` of its workgroup) per chunk at a time; with a ticket counter the waves are persistent (common/lz_launch.hip.h).
+ * A place of the launch (the wave's own first, then one per ticket) is chunk order[place] where the launch has an order
+ * (common/lz_order.hip.h: long chunks first), the chunk of that index otherwise.
  * decode(chunk, err) -> bytes produced, for chunks that are not too long. */
 template <bool CHECKED, class Decode>
 __device__ __forceinline__ void decode_window_loop(const Tickets& launch, uint32_t w, Decode decode)
@@ -58,7 +64,8 @@ __device__ __forceinline__ void decode_window_loop(const Tickets& launch, uint32
     if (place >= a->b.batch_size) {
       break;
     }
-    const size_t chunk = place;
+    const uint32_t* order = a->order;
+    const size_t chunk = order != nullptr ? (size_t)wave::uniform(order[place]) : place;
     const Chunk c = fetch_chunk(&a->b, chunk);
     uint32_t err = lz::kErrNone;
     uint32_t produced = 0;
@@ -228,19 +235,51 @@ static inline nvcompStatus_t decompress_async(
   return checked_launch(batch_size, all_set(comp_ptrs, comp_bytes, out_caps, out_ptrs), [&] {
     if (batch_size <= kTeam16MaxBatch) {
       /* at most one chunk per CU: sixteen waves a chunk (one team holds a whole CU's LDS budget for two) */
-      const Tickets one_each = {b, nullptr, batch_size};
+      const Tickets one_each = {b, nullptr, batch_size, nullptr};
       hipLaunchKernelGGL(Team16, dim3((unsigned)batch_size), dim3(1024), 0, stream, one_each);
     } else if (batch_size <= kTeamMaxBatch) {
       /* small batches cannot fill the card with one wave per chunk: a workgroup per chunk (common/lz_team.hip.h) */
       launch_persistent<Team8>(stream, temp, temp_bytes, batch_size, 1, 512, 0,
-                               [&](uint32_t* ticket, size_t first_dynamic) { return Tickets{b, ticket, first_dynamic}; });
+                               [&](uint32_t* ticket, size_t first_dynamic) { return Tickets{b, ticket, first_dynamic, nullptr}; });
     } else if (batch_size <= kPairMaxBatch) {
       /* (round 2's path for small batches: two waves per chunk, producer / consumer) */
       hipLaunchKernelGGL(Pair, dim3((unsigned)batch_size), dim3(128), 0, stream, b);
     } else {
-      launch_persistent<Window>(stream, temp, temp_bytes, batch_size, kDecWaves, 64 * kDecWaves, NVCOMP_LZ_MAX_WG_PER_CU,
-                                [&](uint32_t* ticket, size_t waves) { return Tickets{b, ticket, waves}; });
+      /* persistent waves; with more chunks than waves and the temp buffer of the size query, long chunks first */
+      launch_persistent_ordered<Window>(
+          stream, temp, temp_bytes, b, kDecWaves, 64 * kDecWaves, NVCOMP_LZ_MAX_WG_PER_CU,
+          [&](uint32_t* ticket, size_t waves, const uint32_t* order) { return Tickets{b, ticket, waves, order}; });
     }
+  });
+}
+
+/* nvcompAmd<format>DecompressOrderAsync (include/nvcomp/amd_ext.h), for tests and scripts: what a persistent decode launch
+ * of the format's Window kernel holds on this card (`resident_places`: waves, = chunks in flight; 0 when the runtime cannot
+ * tell) and, for a batch and a temp buffer, the order pass alone (common/lz_order.hip.h) with the places in front of
+ * `first_ordered` left to their own chunks: `order_offset` is where in the temp buffer the batch_size chunk indices
+ * (uint32) then stand. nvcompErrorInvalidValue when the temp buffer cannot hold them or first_ordered > batch_size.
+ * Either result pointer may be NULL. */
+template <auto Window>
+static inline nvcompStatus_t order_inspect_async(
+    const size_t* comp_bytes, const size_t* out_caps, size_t first_ordered, size_t batch_size, void* temp, size_t temp_bytes,
+    size_t* order_offset, size_t* resident_places, hipStream_t stream)
+{
+  if (resident_places != nullptr) {
+    *resident_places = (size_t)resident_fit<Window>(64 * kDecWaves, NVCOMP_LZ_MAX_WG_PER_CU) * kDecWaves;
+  }
+  if (order_offset == nullptr) {
+    return nvcompSuccess;
+  }
+  return checked_launch(batch_size, all_set(comp_bytes, out_caps), [&]() -> nvcompStatus_t {
+    if (first_ordered > batch_size || !order_fits(temp, temp_bytes, batch_size)) {
+      return nvcompErrorInvalidValue;
+    }
+    const uint32_t* order = order_async(stream, temp, comp_bytes, out_caps, first_ordered, batch_size);
+    if (order == nullptr) {
+      return nvcompErrorCudaError;
+    }
+    *order_offset = (size_t)((const uint8_t*)order - (const uint8_t*)temp);
+    return nvcompSuccess;
   });
 }
 

@@ -10,6 +10,17 @@
  * stream in front of the kernel; without a temp buffer (a caller that passes NULL) the launch falls back to one
  * wave per chunk, statically.
  *
+ * THE LAST PLACES BY SIZE. When the counter runs out every wave still holds a chunk, and the card empties over the
+ * decode time of the slowest of them. The one-wave decoders therefore run the order pass of common/lz_order.hip.h in
+ * place of that memset (two small launches that read only the call's two size arrays, clear the ticket and write
+ * order[] behind it in the temp buffer): the last places of the launch, as many as it has resident waves, get the last
+ * chunks of the batch by descending compressed size, chunks stored nearly raw at the very end; every place in front of
+ * them keeps the chunk of its own index, so the bulk of the launch runs on the batch's own mix (the whole launch by
+ * descending size is 2.6 % SLOWER than index order: DESIGN.md section 6). It runs when the launch has more chunks than
+ * resident waves and the temp buffer holds the order (nvcompBatched<Fmt>DecompressGetTempSize asks for it from 7 169 chunks on); with a
+ * smaller buffer the launch is the ticket's alone, with none the static one. The team and pair kernels and the
+ * compressors hand out in index order.
+ *
  * PATH BY BATCH SIZE. Batches of at most kTeamMaxBatch chunks cannot fill the card with one wave per chunk and run a
  * WORKGROUP of eight waves per chunk (common/lz_team.hip.h); kPairMaxBatch is the same for round 2's two waves per chunk
  * (producer / consumer, common/lz_pair.hip.h), which the team supersedes where both apply. The thresholds are
